@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload zinc|qm9|regular|zinc_gd16] [--batch B]
                     [--model KPGINPlus|KPGIN] [--combine geometric|attention] [--dense-peripheral]
+                    [--full] [--dump-outputs DIR]
 
 Default workload = BASELINE.json configs[1] (reference README.md:127 `train_ZINC.py --residual --K=8
 --model_name=KPGINPlus --num_layer=8 --hidden_size=104`): GNNPlus body, K=8, L=8, h=104, geometric combine, JK=concat,
@@ -21,11 +22,17 @@ ranks, model replicated, one RCCL all-reduce of the flat gradient bucket per ste
 --scaling strong: --batch is ONE global batch, partitioned over the ranks by active pairs (dp.partition_by_pairs), each rank's
 mean loss weighted by its share of the graphs (dp.shard_loss_weight), gradients summed.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0) with the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step = wall milliseconds of one timed step).  --full adds
   "roofline":     HIP-event timing of the aggregation kernel launches vs the algorithmic bytes of SURVEY.md 8(d)
-                  (HBM bound, peak 8 TB/s), with the workload's own A and D;
+                  (HBM bound, peak 8 TB/s), with the workload's own A and D (off with --no-roofline);
   "cpu_baseline": the oracle ("port": oracle/, the reference's materialised [E,K,D] op sequence in plain PyTorch)
-                  timed on this box's host cores on a bounded sample of the same workload.
+                  timed on this box's host cores on a bounded sample of the same workload (off with --no-cpu-baseline).
+--dump-outputs DIR: after the timed steps, what the last timed step produced goes to DIR/<name>.npy (fp32): `loss`, the
+flat gradient bucket `grad` and the flat parameter bucket `params` after its optimiser step; `output` for the
+forward-only workload.  Batches and initial weights are seeded, and the last timed step of a training workload starts
+from that seeded initial state (weights, Adam moments, step number) rather than from the state the steps before it left:
+equal arguments give that step equal inputs on every run, and its outputs differ by the kernels' rounding alone.
 """
 import argparse
 import hashlib
@@ -40,7 +47,8 @@ dp = None
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md); ~6.3 TB/s achievable
+HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak; ~6.3 TB/s achievable
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all arrays together (under 64 MB with the .npy headers)
 T_START = time.perf_counter()
 
 
@@ -263,6 +271,45 @@ def cpu_baseline(args, state_dict, threads):
             "sample": f"{nb} graphs x {args.cpu_iters} {what} iterations (median), oracle/, torch {torch.__version__} CPU"}
 
 
+def initial_state(opt):
+    """What a training step reads besides its batch - the weights, the Adam moments and the step number - as it is now;
+    returns restore(), which puts it back in place (the captured graphs keep their pointers).  The BatchNorm running
+    statistics are left alone: a training-mode forward writes them but does not read them."""
+    from kp_gnn_amd.ops_dense import invalidate_splits
+    live = [opt.param.data, opt.exp_avg, opt.exp_avg_sq] + ([opt.state] if opt.state is not None else [])
+    saved, steps = [t.clone() for t in live], opt.steps
+
+    def restore():
+        torch._foreach_copy_(live, saved)
+        opt.steps = steps
+        invalidate_splits()      # (as after an optimiser step: the weights changed without a version bump)
+    return restore
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as out_dir/<name>.npy, float64 kept, everything else
+    fp32, DUMP_BUDGET_BYTES in all: arrays are kept whole smallest first; one that does not fit into its even share of
+    what is left keeps a fixed seeded sample of its flattened elements (in index order), so two runs with the same
+    arguments write the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+    left = DUMP_BUDGET_BYTES
+    order = sorted(host, key=lambda n: host[n].nbytes)
+    for i, name in enumerate(order):
+        a = host[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(host)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -281,10 +328,16 @@ def main():
                          "(KPGNN_STORE_BF16, KP-GIN+ path); every parameter, state and accumulator stays fp32")
     ap.add_argument("--dense-peripheral", action="store_true",
                     help="hand the layers the dense [N,K,D] peripheral tensor instead of its dictionary form")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also run the secondary legs: per-launch HIP-event timing + roofline, CPU "
+                         "oracle baseline (a plain run only sets up, warms up, times --steps steps and prints the result)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (loss, grad, params; output when forward-only); "
+                         "that step starts from the seeded initial weights and optimiser state")
     ap.add_argument("--cpu-graphs", type=int, default=128)
     ap.add_argument("--cpu-iters", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the per-launch HIP-event timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the per-launch HIP-event timing")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly (no hipGraph replay)")
     ap.add_argument("--adam-in-graph", action="store_true",
                     help="1 GPU: capture the optimiser step (device-side step number) in the graph; measured 20 us SLOWER per step "
@@ -401,7 +454,7 @@ def main():
             f"(N={batches[0].num_nodes}, E_khop={batches[0].csr.E}, A={batches[0].csr.A})")
 
     model = build_model(args, device)
-    flat_grad = opt = None
+    flat_grad = flat_param = opt = None
     if args.train:
         if world > 1:  # identical replicas
             dp.broadcast_model(model)
@@ -410,6 +463,11 @@ def main():
         flat_param.grad = flat_grad
         # elementwise: identical to per-parameter Adam (train_ZINC.py:244)
         opt = dp.FlatAdam(flat_param, flat_grad, lr=1e-3, device_step=(world == 1 and not args.no_graph and args.adam_in_graph))
+    # --dump-outputs: the last timed step starts again from the seeded initial state, so what it computes depends on the
+    # arguments alone.  Carried over from the steps before it, the state would not: the kernels' float atomics round in
+    # the order the hardware runs them, and Adam turns such differences in near-zero gradients into lr-sized steps that
+    # compound from step to step.
+    reset_state = initial_state(opt) if (args.dump_outputs and args.train) else None
 
     def barrier():
         torch.cuda.synchronize()
@@ -466,6 +524,8 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if reset_state is not None and i == args.steps - 1:
+            reset_state()              # (three or four device copies, queued ahead of the last step)
         if sampler is not None:        # a batch no step has seen: collated from the resident dataset, here, in the timed region
             ids = sampler()
             if static_graph is not None:
@@ -488,10 +548,14 @@ def main():
     final = float(out_t.float().abs().mean().item()) if not args.train else float(out_t.item())
     if rank == 0:
         log(f"timed {args.steps} steps in {elapsed:.3f}s")
+    if args.dump_outputs and rank == 0:    # before anything else steps the model again
+        arrays = {"loss": out_t, "grad": flat_grad, "params": flat_param} if args.train else {"output": out_t}
+        names = dump_outputs(args.dump_outputs, arrays)
+        log(f"last timed step's {', '.join(names)} written to {args.dump_outputs}")
     # Per-launch kernel timing (roofline leg): HIP events around every aggregation launch, on the launch
     # stream, over the same K steps run eagerly (events cannot bracket single kernels inside a replayed graph).
     timer = None
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         timer = ops.LaunchTimer()
         ops.set_launch_timer(timer)
         train_step(args, model, batches[0], opt, flat_grad, 1)  # primes the byte-accounting caches
@@ -574,7 +638,7 @@ def main():
                                        "launches": g["launches"], "avg_launch_ms": round(g["avg_ms"], 4),
                                        "algorithmic_bytes_per_launch": int(g["bytes_per_launch"])}
                 out["roofline_bwd"].update(pmc_traffic(args, "agg_pull_kernel" if pull else "agg_bwd_kernel"))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sd = {k: v for k, v in model.state_dict().items()}
             log(f"cpu baseline: oracle on {threads} host threads ...")
             out["cpu_baseline"] = cpu_baseline(args, sd, threads)

@@ -1,6 +1,6 @@
 # Round-3 measurements, one gpurun call:  bash scripts/measure_round.sh   -> gpurun_out/r03fin/ (copy what is judged to profiles/r03/)
 cd $GRAFT_REPO_ROOT && R=$GRAFT_REPO_ROOT/gpurun_out/r03fin && rm -rf $R && mkdir -p $R
-B="python bench.py"
+B="python bench.py --full"
 PB="python3 $GRAFT_REPO_ROOT/bench.py"
 run() { name=$1; shift; timeout -k 10 400 $B "$@" > $R/$name.json 2> $R/$name.log; echo "$name rc=$?"; }
 timeout -k 10 900 python -m pytest tests -q -m gpu > $R/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -2 $R/pytest_gpu.log

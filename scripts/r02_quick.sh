@@ -2,7 +2,7 @@
 # kernel-trace of the default line -> gpurun_out/q/   usage: bash scripts/r02_quick.sh [notest]
 cd $GRAFT_REPO_ROOT && R=$GRAFT_REPO_ROOT/gpurun_out/q && mkdir -p $R
 if [ "$1" != "notest" ]; then timeout -k 10 900 python -m pytest tests -q -m gpu -x > $R/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -2 $R/pytest_gpu.log; fi
-run() { name=$1; shift; timeout -k 10 400 python bench.py "$@" > $R/$name.json 2> $R/$name.log; echo "$name rc=$? $(cut -c90-220 $R/$name.json)"; }
+run() { name=$1; shift; timeout -k 10 400 python bench.py --full "$@" > $R/$name.json 2> $R/$name.log; echo "$name rc=$? $(cut -c90-220 $R/$name.json)"; }
 run bench_default --no-cpu-baseline
 run bench_b64 --batch 64 --steps 100 --no-cpu-baseline
 run bench_dense --dense-peripheral --no-cpu-baseline

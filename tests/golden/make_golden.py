@@ -15,6 +15,7 @@ gather / scatter-sum is pinned only through its documented contract.
 Only *data* is written: inputs, seeded weights, outputs and gradients as tensors.  No reference
 source text or bytecode is stored (sys.dont_write_bytecode is set and nothing is copied).
 """
+import glob
 import os
 import sys
 
@@ -44,6 +45,42 @@ from models.GraphRegression import GraphRegression  # noqa: E402
 from models.model_utils import make_GNN  # noqa: E402
 
 torch.set_num_threads(1)
+
+PART_BYTES = 768_000   # tensor bytes per file: with the per-entry overhead every fixture stays below 1 MiB
+
+
+def save_cases(cases, outdir, name):
+    """torch.save(cases) as <name>.pt, or - past PART_BYTES of tensor data - as <name>.part00.pt, .part01.pt, ...:
+    the leaves of the nested dicts in their order, each part a nested dict of its run of leaves
+    (tests/conftest.py merges the parts back into one dict)."""
+    leaves = []
+
+    def walk(d, path):
+        for k, v in d.items():
+            if isinstance(v, dict) and v:
+                walk(v, path + (k,))
+            else:
+                leaves.append((path + (k,), v, v.numel() * v.element_size() if torch.is_tensor(v) else 0))
+
+    walk(cases, ())
+    for f in glob.glob(os.path.join(outdir, glob.escape(name) + ".part[0-9][0-9].pt")) + [os.path.join(outdir, name + ".pt")]:
+        if os.path.exists(f):      # (the loader takes <name>.pt over parts: nothing of an earlier run may stay)
+            os.remove(f)
+    if sum(n for _, _, n in leaves) <= PART_BYTES:
+        torch.save(cases, os.path.join(outdir, name + ".pt"))
+        return
+    parts, size = [{}], 0
+    for path, v, n in leaves:
+        if size and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        d = parts[-1]
+        for k in path[:-1]:
+            d = d.setdefault(k, {})
+        d[path[-1]] = v
+        size += n
+    for i, part in enumerate(parts):
+        torch.save(part, os.path.join(outdir, f"{name}.part{i:02d}.pt"))
 
 
 # ----------------------------------------------------------------------------- input graphs
@@ -342,7 +379,7 @@ def make_layer_goldens(outdir):
     cases["kpsage_k1_h8"] = layer_case(
         "KPGraphSAGE", dict(input_size=8, output_size=8, K=1, aggr="add", num_hop1_edge=1, num_pe=10),
         ["path5", "reg3_n20_s0"], "tu_k3_spd", 43, with_periph=False)
-    torch.save(cases, os.path.join(outdir, "layers.pt"))
+    save_cases(cases, outdir, "layers")
     print(f"layers.pt: {len(cases)} cases")
 
 
@@ -371,7 +408,7 @@ def make_combine_goldens(outdir):
         (out * w).sum().backward()
         cases[name] = {"x": x.detach().clone(), "out": out.detach(), "out_weight": w, "grad_x": x.grad.clone(),
                        "state_dict": {k: v.clone() for k, v in m.state_dict().items()}, "param_grads": grads_of(m)}
-    torch.save(cases, os.path.join(outdir, "combine.pt"))
+    save_cases(cases, outdir, "combine")
     print(f"combine.pt: {len(cases)} cases")
 
 
@@ -426,7 +463,7 @@ def make_body_goldens(outdir):
                                                  ["mol_2", "mol_3"], 65, residual=False, JK="sum")
     cases["gnnprime_k3_l3_h18_geo"] = body_case("KPGINPrime", 3, 3, 18, "geometric", "zinc_k3_gd",
                                                 ["mol_0", "mol_3"], 66)
-    torch.save(cases, os.path.join(outdir, "bodies.pt"))
+    save_cases(cases, outdir, "bodies")
     print(f"bodies.pt: {len(cases)} cases")
 
 
@@ -475,7 +512,7 @@ def make_kgin_goldens(outdir):
         cases[name] = {"K": K, "hidden_size": hs, "pool": pool, "state_dict": sd, "x": x.detach().clone(),
                        "edge_index": b.edge_index.clone(), "edge_attr": b.edge_attr.clone(), "batch": b.batch.clone(),
                        "out": out.detach().clone(), "out_weight": w, "grad_x": x.grad.clone(), "param_grads": grads_of(layer)}
-    torch.save(cases, os.path.join(outdir, "kgin.pt"))
+    save_cases(cases, outdir, "kgin")
     print(f"kgin.pt: {len(cases)} cases")
 
 

@@ -1,7 +1,5 @@
 """GPU (-m gpu): the HIP path, called through the C ABI, against (a) the golden vectors produced by the
 reference's own layer files and (b) the CPU oracle on seeded inputs.  fp32; tolerances written below."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -121,12 +119,12 @@ def _make_layer(case):
     return layer.to(_dev()).train()
 
 
-def _layer_cases(golden_dir):
-    return torch.load(os.path.join(golden_dir, "layers.pt"), weights_only=True)
+def _layer_cases(golden_cases):
+    return golden_cases("layers")
 
 
-def test_layers_match_reference_goldens(golden_dir):
-    cases = _layer_cases(golden_dir)
+def test_layers_match_reference_goldens(golden_cases):
+    cases = _layer_cases(golden_cases)
     dev = _dev()
     for name, case in cases.items():
         layer = _make_layer(case)
@@ -316,9 +314,9 @@ def _build_body(case):
     return model
 
 
-def test_bodies_match_reference_goldens(golden_dir):
+def test_bodies_match_reference_goldens(golden_cases):
     """GNN / GNNPlus / GNNPrime + GraphRegression, L1 loss, fwd+bwd: score, loss, every parameter grad."""
-    cases = torch.load(os.path.join(golden_dir, "bodies.pt"), weights_only=True)
+    cases = golden_cases("bodies")
     dev = _dev()
     for name, case in cases.items():
         model = _build_body(case).to(dev).train()
@@ -405,7 +403,7 @@ def _frob_rel(a, b):
     return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
-def test_bf16_storage_bodies_match_reference_goldens(golden_dir, bf16_storage):
+def test_bf16_storage_bodies_match_reference_goldens(golden_cases, bf16_storage):
     """The KP-GIN+ body of the reference goldens (the bench configuration: K=8, L=8, h=104, geometric) with bf16 storage of
     the K-hop streams against the reference's fp32 CPU results.  Score and loss: 2e-2 of scale.  Parameter gradients:
     this golden batch has 73 nodes in 3 graphs and sixteen training-mode BatchNorms, whose backward subtracts batch means
@@ -414,7 +412,7 @@ def test_bf16_storage_bodies_match_reference_goldens(golden_dir, bf16_storage):
     is that conditioning, not the kernels' accuracy: test_bf16_storage_body_vs_fp32_batch512 measures the same model at
     a realistic batch, where the averaging over nodes brings it to ~1 %."""
     from kp_gnn_amd import ops
-    cases = torch.load(os.path.join(golden_dir, "bodies.pt"), weights_only=True)
+    cases = golden_cases("bodies")
     dev = _dev()
     ran = 0
     for name, case in cases.items():
@@ -797,13 +795,13 @@ def test_linear_wgrad_relu_mask_on_load():
     _close(db, dym.sum(0), "db", rtol=2e-4, atol=2e-5)
 
 
-def test_kgin_layer_matches_reference_goldens(golden_dir):
+def test_kgin_layer_matches_reference_goldens(golden_cases):
     """run_simulation.py's mask-only KGINConv (config 4) on the HIP path against vectors produced by the reference's own
     class (ast-extracted from the script, tests/golden/make_golden.py): output, input gradient, parameter gradients,
     with and without the script's `args.graph` sum pooling."""
     from kp_gnn_amd.layers import KGINConv
     dev = _dev()
-    cases = torch.load(os.path.join(golden_dir, "kgin.pt"), weights_only=True)
+    cases = golden_cases("kgin")
     assert len(cases) >= 3
     for name, c in cases.items():
         layer = KGINConv(c["hidden_size"], c["K"], pool=bool(c["pool"]))
@@ -840,11 +838,11 @@ def test_kgin_config4_shape_vs_oracle():
     _close(got, ref, "out", rtol=2e-4, atol=2e-5)
 
 
-def test_attention_combine_hip_vs_reference_goldens(golden_dir):
+def test_attention_combine_hip_vs_reference_goldens(golden_cases):
     """AttentionCombine on the HIP kernels (recurrence, softmax, BPTT, MFMA weight grads) vs the reference's nn.LSTM."""
     from kp_gnn_amd.layers import AttentionCombine
     dev = _dev()
-    cases = torch.load(os.path.join(golden_dir, "combine.pt"), weights_only=True)
+    cases = golden_cases("combine")
     n = 0
     for name, case in cases.items():
         if not name.startswith("att"):

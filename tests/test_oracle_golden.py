@@ -84,8 +84,8 @@ def _run_layer(case):
     return p, x, periph, out
 
 
-def test_layer_oracle_matches_reference(golden_dir):
-    cases = torch.load(os.path.join(golden_dir, "layers.pt"), weights_only=True)
+def test_layer_oracle_matches_reference(golden_cases):
+    cases = golden_cases("layers")
     assert len(cases) >= 22
     for name, case in cases.items():
         p, x, periph, out = _run_layer(case)
@@ -105,8 +105,8 @@ def test_layer_oracle_matches_reference(golden_dir):
                 _close(p[k], v, f"{name}:{k}")
 
 
-def test_combine_oracle_matches_reference(golden_dir):
-    cases = torch.load(os.path.join(golden_dir, "combine.pt"), weights_only=True)
+def test_combine_oracle_matches_reference(golden_cases):
+    cases = golden_cases("combine")
     for name, case in cases.items():
         p = _leafify(case["state_dict"], case["param_grads"])
         x = case["x"].clone().requires_grad_(True)
@@ -118,9 +118,9 @@ def test_combine_oracle_matches_reference(golden_dir):
             _close(p[k].grad, g, f"{name}:grad[{k}]", rtol=1e-4, atol=1e-5)
 
 
-def test_path_encoding_table_never_trains(golden_dir):
+def test_path_encoding_table_never_trains(golden_cases):
     """Q1: pe_attr is all-zero, row 0 is the padding row -> hopk_node_path_emb gets exactly zero grad."""
-    cases = torch.load(os.path.join(golden_dir, "layers.pt"), weights_only=True)
+    cases = golden_cases("layers")
     for name, case in cases.items():
         g = case["param_grads"].get("hopk_node_path_emb.weight")
         if g is not None:
@@ -132,9 +132,9 @@ BODY_KIND = {"KPGINPlus": ("GNNPlus", "KPGINPlus"), "KPGIN": ("GNN", "KPGIN"), "
              "KPGINPrime": ("GNNPrime", "KPGIN")}
 
 
-def test_body_oracle_matches_reference(golden_dir):
+def test_body_oracle_matches_reference(golden_cases):
     from oracle import kp_model_oracle as MO
-    cases = torch.load(os.path.join(golden_dir, "bodies.pt"), weights_only=True)
+    cases = golden_cases("bodies")
     assert len(cases) >= 6
     for name, case in cases.items():
         kind, layer_kind = BODY_KIND[case["model_name"]]
@@ -154,10 +154,10 @@ def test_body_oracle_matches_reference(golden_dir):
                 (name, k, float((got - g).abs().max()), gscale)
 
 
-def test_kgin_oracle_matches_reference_goldens(golden_dir):
+def test_kgin_oracle_matches_reference_goldens(golden_cases):
     """oracle.kgin_forward (run_simulation.py's mask-only KGINConv) against vectors produced by the reference's own class
     (cut out of run_simulation.py with ast and executed alone, tests/golden/make_golden.py): output and every gradient."""
-    cases = torch.load(os.path.join(golden_dir, "kgin.pt"), weights_only=True)
+    cases = golden_cases("kgin")
     assert len(cases) >= 3
     for name, c in cases.items():
         p = {k: v.clone().requires_grad_(v.is_floating_point() and k != "eps") for k, v in c["state_dict"].items()}
