@@ -290,6 +290,11 @@ typedef struct kpgnn_agg_fwd_desc {
 
 int kpgnn_aggregate_fwd(const kpgnn_agg_fwd_desc* d, kpgnn_stream_t stream);
 
+/* How many kpgnn_aggregate_fwd calls of this process were served by the LDS-staged kernel (graph_ptr given and every
+ * condition above met).  A host-side counter: the choice of kernel leaves no other trace, so a test of that kernel reads it
+ * before and after its call. */
+int64_t kpgnn_agg_lds_launch_count(void);
+
 /* Backward of the aggregation w.r.t. x and the two edge-code tables, given g = dL/dS [N,K,D]
  * (the caller applies the activation derivative; for GCN g already includes relu').
  *   gx[j,k,:]      = sum over pairs a of segment (j,k) of the BY-SOURCE csr of w_a * g[col[a],k,:]  (+ self terms)

@@ -697,6 +697,8 @@ int launch_bwd_mode(const BwdParams& p, int tab, size_t lds, hipStream_t s) {
 
 using namespace kpgnn;
 
+extern "C" int64_t kpgnn_agg_lds_launch_count(void) { return agg_lds_launch_count(); }
+
 extern "C" int kpgnn_aggregate_fwd(const kpgnn_agg_fwd_desc* d, kpgnn_stream_t stream) {
     KPGNN_REQUIRE(d != nullptr, "aggregate_fwd: NULL descriptor");
     KPGNN_REQUIRE(d->N >= 0 && d->K >= 1 && d->D >= 1 && d->K_csr >= d->K, "aggregate_fwd: bad N=%d K=%d D=%d K_csr=%d",

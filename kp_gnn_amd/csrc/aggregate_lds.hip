@@ -9,6 +9,8 @@
 // loads), then its sub-groups walk their destination nodes' pair lists and take every neighbour row from LDS (ds_read_b128).
 // Only the pair lists and the output stream through HBM.  Pairs are added in list order, like every other kernel of
 // kpgnn_aggregate_fwd (the reference's index_add_ order): results do not depend on which kernel ran.
+#include <atomic>
+
 #include "kpgnn_common.h"
 
 namespace kpgnn {
@@ -85,7 +87,11 @@ agg_lds_fwd_kernel(const LdsAggParams p) {
     }
 }
 
+std::atomic<int64_t> g_lds_launches{0};     // host side, per process: launches of agg_lds_fwd_kernel (kpgnn_agg_lds_launch_count)
+
 }  // namespace
+
+int64_t agg_lds_launch_count() { return g_lds_launches.load(std::memory_order_relaxed); }
 
 // Returns KPGNN_OK with *handled = true when the launch was done here; *handled = false leaves it to the other kernels.
 int agg_lds_fwd(const kpgnn_agg_fwd_desc* d, hipStream_t s, bool* handled) {
@@ -123,6 +129,7 @@ int agg_lds_fwd(const kpgnn_agg_fwd_desc* d, hipStream_t s, bool* handled) {
     }
 #undef KP_LDSAGG
     KPGNN_LAUNCH_CHECK("agg_lds_fwd_kernel");
+    g_lds_launches.fetch_add(1, std::memory_order_relaxed);
     *handled = true;
     return KPGNN_OK;
 }

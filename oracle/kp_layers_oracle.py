@@ -160,9 +160,9 @@ def kpginplus_forward(p, x, edge_index, edge_attr, pe_attr=None, peripheral_attr
     return mlp_bn(p, "mlp", combine(p, x_n, K, combine_kind), training)
 
 
-def khop_degree(index, num_nodes, index_mask):
-    """layers/KPGCN.py:11-25."""
-    out = torch.zeros((num_nodes, index_mask.size(-1)))
+def khop_degree(index, num_nodes, index_mask, dtype=torch.float32):
+    """layers/KPGCN.py:11-25 (there in the default dtype; here in the dtype of the layer's input)."""
+    out = torch.zeros((num_nodes, index_mask.size(-1)), dtype=dtype)
     one = (index_mask > 0).to(out.dtype)
     return out.scatter_add_(0, index.unsqueeze(-1).expand(-1, index_mask.size(-1)), one)
 
@@ -179,7 +179,7 @@ def kpgcn_forward(p, x, edge_index, edge_attr, pe_attr=None, peripheral_attr=Non
     x = add_path_encoding(p, x, pe_attr, K)
     e_emb = edge_code_embedding(p, edge_attr, K)
     row, col = edge_index
-    deg = khop_degree(col, N, edge_attr)
+    deg = khop_degree(col, N, edge_attr, x.dtype)
     dis = deg.pow(-0.5)
     norm = dis[row] * dis[col]
     x_j = x.index_select(0, row)

@@ -59,7 +59,7 @@ def body_forward(p, data, *, kind, layer_kind, K, num_layer, combine_kind, JK="c
     H = x.size(1)
     gate = torch.tanh if kind == "GNNPlus" else torch.sigmoid
     width = H if kind == "GNNPlus" else H // K
-    periph = torch.zeros(N, K, width)
+    periph = torch.zeros(N, K, width, dtype=x.dtype)
     if data.get("peripheral_edge_attr") is not None and "pew" in p:
         periph = periph + gate(p["pew"]) * feature_concat_encoder(sub(p, "peripheral_edge_embedding"),
                                                                   data["peripheral_edge_attr"]).sum(-2)

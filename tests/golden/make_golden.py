@@ -467,6 +467,53 @@ def make_body_goldens(outdir):
     print(f"bodies.pt: {len(cases)} cases")
 
 
+# ----------------------------------------------------------------------------- one body at bench size, float64
+def make_body_n5k_goldens(outdir):
+    """`gnnplus_k8_l8_h104_geo_n5k`: the reference's GNNPlus + GraphRegression in FLOAT64 on the batch and the weights the
+    large-batch GPU tests use (tests/parity_f64.py small_body, kp_gnn_amd.batch.synthetic_zinc_batch(220, seed0=11, K=8):
+    N = 5148), so that the oracle is pinned where those tests use it.  Stored: loss, the 220 scores, every parameter gradient
+    (float64) and a sha256 over inputs + state dict - the test rebuilds both from their seeds.
+    Run under torch.set_default_dtype(float64) and not only .double(): the reference makes some intermediates in the default
+    dtype (GeometricCombine.geometric_distribution assigns into torch.zeros(...)), which would round theta to fp32."""
+    sys.path.insert(0, os.path.join(HERE, ".."))          # tests/parity_f64.py
+    sys.path.insert(0, os.path.join(HERE, "..", ".."))    # kp_gnn_amd
+    import parity_f64 as PF
+    from kp_gnn_amd.batch import synthetic_zinc_batch
+    K, L, h = 8, 8, 104
+    sd = {k: v.detach().clone() for k, v in PF.small_body("KPGINPlus", "geometric", K, L, h).state_dict().items()}
+    host = synthetic_zinc_batch(220, seed0=11, K=K)
+    inputs = host.as_dict()
+    before = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    torch.set_num_threads(8)
+    try:
+        args = argparse.Namespace(model_name="KPGINPlus", hidden_size=h, K=K, num_layer=L, num_hop1_edge=3, max_pe_num=50,
+                                  combine="geometric", eps=0., train_eps=False, aggr="add")
+        gnn = make_GNN(args)(num_layer=L, gnn_layer=make_gnn_layer(args), JK="concat", norm_type="Batch",
+                             init_emb=EmbeddingEncoder(21, h), residual=True, virtual_node=False, use_rd=False, num_hop1_edge=3,
+                             max_edge_count=50, max_hop_num=6, max_distance_count=50, wo_peripheral_edge=False,
+                             wo_peripheral_configuration=False, drop_prob=0.0)
+        model = GraphRegression(embedding_model=gnn, pooling_method="sum").double()
+        model.load_state_dict(sd, strict=True)
+        assert all(p.dtype == torch.float64 for p in model.parameters())
+        model.train()
+        b = Batch(**{k: v.clone() for k, v in inputs.items() if k != "y"})
+        score = model(b)
+        loss = (score.squeeze() - host.y.double().squeeze()).abs().mean()
+        loss.backward()
+        grads = grads_of(model)
+    finally:
+        torch.set_default_dtype(before)
+        torch.set_num_threads(1)
+    assert score.dtype == torch.float64 and loss.dtype == torch.float64 and tuple(score.shape) == (220,)
+    assert all(g.dtype == torch.float64 for g in grads.values())
+    case = {"model_name": "KPGINPlus", "K": K, "L": L, "h": h, "combine": "geometric", "graphs": 220, "seed0": 11,
+            "num_nodes": host.num_nodes, "sha256": PF.tensors_sha256(inputs, sd),
+            "score": score.detach(), "loss": loss.detach(), "param_grads": grads}
+    save_cases({"gnnplus_k8_l8_h104_geo_n5k": case}, outdir, "bodies_n5k")
+    print(f"bodies_n5k: N = {host.num_nodes}, sha256 {case['sha256'][:16]}, loss {float(loss.detach()):.12f}")
+
+
 # ----------------------------------------------------------------------------- run_simulation.py's KGINConv
 def reference_kgin_class(graph_pool):
     """The reference's `KGINConv` (run_simulation.py:29-93) WITHOUT running the script: run_simulation.py has no
@@ -517,7 +564,9 @@ def make_kgin_goldens(outdir):
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["pre", "layers", "combine", "bodies", "kgin"]
+    which = sys.argv[1:] or ["pre", "layers", "combine", "bodies", "kgin", "bodies_n5k"]
+    if "bodies_n5k" in which:
+        make_body_n5k_goldens(HERE)
     if "kgin" in which:
         make_kgin_goldens(HERE)
     if "pre" in which:
