@@ -3,6 +3,8 @@ or a call fails, an exception is raised - the product path never silently runs o
 import ctypes
 import os
 
+import torch
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "libkpgnn_hip.so")
 
@@ -380,3 +382,52 @@ def check(rc, what):
     if rc != 0:
         msg = load().kpgnn_last_error()
         raise KpgnnError(f"{what} failed (rc={rc}): {msg.decode() if msg else '?'}")
+
+
+class LaunchTimer:
+    """Opt-in per-launch timing of the aggregation kernels with HIP events recorded on the stream the
+    kernel is launched on (bench.py's roofline leg).  Each record: (kind, algorithmic_bytes, start, stop)."""
+
+    def __init__(self):
+        self.records = []
+
+    def summary(self):
+        """kind -> dict(launches, avg_ms, bytes_per_launch, gbps); call after a device synchronize."""
+        out = {}
+        for kind, nbytes, a, b in self.records:
+            d = out.setdefault(kind, {"launches": 0, "ms": 0.0, "bytes": 0})
+            d["launches"] += 1
+            d["ms"] += a.elapsed_time(b)
+            d["bytes"] += nbytes
+        for d in out.values():
+            d["avg_ms"] = d["ms"] / d["launches"]
+            d["bytes_per_launch"] = d["bytes"] / d["launches"]
+            d["gbps"] = d["bytes"] / (d["ms"] * 1e-3) / 1e9 if d["ms"] > 0 else 0.0
+        return out
+
+
+_timer = None
+
+
+def set_launch_timer(timer):
+    global _timer
+    _timer = timer
+
+
+def launch(name, dev, *args, timed=None):
+    """Call the entry point `name` on the current stream of `dev` (appended as the last argument) and check its return code.
+    timed = (kind, nbytes_fn): with a launch timer installed the call is bracketed by two events and recorded as
+    (kind, nbytes_fn(), start, stop).  nbytes_fn runs only then: a byte count may synchronise with the device, which an
+    untimed step (let alone a stream capture) must not."""
+    fn = getattr(_lib or load(), name)
+    with torch.cuda.device(dev):
+        timer = _timer if timed is not None else None
+        if timer is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        rc = fn(*args, torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            check(rc, name)
+        if timer is not None:
+            e1.record()
+            timer.records.append((timed[0], timed[1](), e0, e1))

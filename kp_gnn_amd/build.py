@@ -59,6 +59,13 @@ def _compile(compiler, flags, src):
     return obj
 
 
+def _jobs():
+    """Compile jobs: MAX_JOBS if set, else up to 16 (a shared host shows every CPU of the machine, not the share of one command)."""
+    if os.environ.get("MAX_JOBS"):
+        return max(2, int(os.environ["MAX_JOBS"]))
+    return max(2, min(16, (os.cpu_count() or 4) - 1))
+
+
 def build_hip(force=False):
     srcs = _sources(".hip")
     if not force and not _stale(HIP_LIB, srcs + _headers()):
@@ -68,7 +75,7 @@ def build_hip(force=False):
         for f in os.listdir(OBJ):
             if f.endswith(".hip.o"):
                 os.remove(os.path.join(OBJ, f))
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(max(2, (os.cpu_count() or 4) - 1), len(srcs))) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=min(_jobs(), len(srcs))) as ex:
         objs = list(ex.map(lambda s: _compile(HIPCC, HIP_FLAGS, s), srcs))
     _run([HIPCC, "-shared", "--offload-arch=gfx950", "-o", HIP_LIB] + objs)
     return HIP_LIB

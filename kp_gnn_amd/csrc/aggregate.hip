@@ -25,27 +25,11 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kMaxLdsTableBytes = 96 * 1024;
 
-template <int VEC> struct Vec;
-template <> struct Vec<1> { using T = float; };
-template <> struct Vec<2> { using T = float2; };
-template <> struct Vec<4> { using T = float4; };
-
 template <int VEC> struct V {
     float v[VEC];
     __device__ __forceinline__ static V zero() { V r; for (int i = 0; i < VEC; ++i) r.v[i] = 0.f; return r; }
-    __device__ __forceinline__ static V load(const float* p) {
-        V r;
-        typename Vec<VEC>::T t = *reinterpret_cast<const typename Vec<VEC>::T*>(p);
-        const float* f = reinterpret_cast<const float*>(&t);
-        for (int i = 0; i < VEC; ++i) r.v[i] = f[i];
-        return r;
-    }
-    __device__ __forceinline__ void store(float* p) const {
-        typename Vec<VEC>::T t;
-        float* f = reinterpret_cast<float*>(&t);
-        for (int i = 0; i < VEC; ++i) f[i] = v[i];
-        *reinterpret_cast<typename Vec<VEC>::T*>(p) = t;
-    }
+    __device__ __forceinline__ static V load(const float* p) { V r; ldv<VEC>(p, r.v); return r; }
+    __device__ __forceinline__ void store(float* p) const { stv<VEC>(p, v); }
     // streaming store (nt): for rows nobody re-reads in this launch - they should not displace the gathered rows in L2
     __device__ __forceinline__ void store_stream(float* p) const {
         for (int i = 0; i < VEC; ++i) __builtin_nontemporal_store(v[i], p + i);
@@ -583,32 +567,6 @@ agg_bwd_kernel(const BwdParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------- dispatch
-struct Shape { int vec, g; };
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
-
-int pick_vec(int D, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> strides) {
-    int vec = 4;
-    if (D % 4 != 0) vec = (D % 2 == 0) ? 2 : 1;
-    for (const void* q : ptrs) {
-        if (!q) continue;
-        if (vec == 4 && !aligned16(q)) vec = aligned8(q) ? 2 : 1;
-        if (vec == 2 && !aligned8(q)) vec = 1;
-    }
-    for (int64_t s : strides) {
-        if (vec == 4 && s % 4 != 0) vec = (s % 2 == 0) ? 2 : 1;
-        if (vec == 2 && s % 2 != 0) vec = 1;
-    }
-    return vec;
-}
-
-int pick_group(int lanes_needed) {
-    int g = 4;
-    while (g < lanes_needed) g <<= 1;
-    return g;
-}
-
 unsigned pick_grid(int64_t num_tiles, int blocks_per_cu) {
     const int64_t cap = (int64_t)device_facts().cu_count * blocks_per_cu;
     int64_t g = num_tiles < cap ? num_tiles : cap;
@@ -680,17 +638,6 @@ int launch_bwd_mode(const BwdParams& p, int tab, size_t lds, hipStream_t s) {
         default: return gcn ? launch_bwd<VEC, G, true, 2>(p, 0, s) : launch_bwd<VEC, G, false, 2>(p, 0, s);
     }
 }
-
-// (VEC, G) pairs instantiated: G in {4,8,16,32,64}, G*VEC >= D  (D <= 256 for VEC 4).
-#define KP_DISPATCH_SHAPE(CALL)                                                                    \
-    switch (vec * 100 + g) {                                                                       \
-        case 404: return CALL(4, 4); case 408: return CALL(4, 8); case 416: return CALL(4, 16);    \
-        case 432: return CALL(4, 32); case 464: return CALL(4, 64);                                \
-        case 204: return CALL(2, 4); case 208: return CALL(2, 8); case 216: return CALL(2, 16);    \
-        case 232: return CALL(2, 32); case 264: return CALL(2, 64);                                \
-        case 104: return CALL(1, 4); case 108: return CALL(1, 8); case 116: return CALL(1, 16);    \
-        case 132: return CALL(1, 32); case 164: return CALL(1, 64);                                \
-    }
 
 }  // namespace
 }  // namespace kpgnn
@@ -776,17 +723,14 @@ extern "C" int kpgnn_aggregate_fwd(const kpgnn_agg_fwd_desc* d, kpgnn_stream_t s
     const void* slot_align = (const void*)(slot_bits | 16);   // synthetic address carrying that alignment (never dereferenced)
     if ((uint64_t)d->N * (uint64_t)d->x_sn * 4u >= (1ull << 32))
         return fail(KPGNN_ELIMIT, "aggregate_fwd: N * x row stride = %lld floats exceeds the 32-bit byte offsets of the gather", (long long)d->N * d->x_sn);
-    const int vec = pick_vec(d->D, {d->x ? (const void*)d->x : slot_align, d->periph, d->out, d->pre, d->table0, d->tablek, d->theta, d->hout, d->hinit, d->hinit2, d->xbias, d->periph ? nullptr : d->ptab},
+    const int vec = row_vec(d->D, {d->x ? (const void*)d->x : slot_align, d->periph, d->out, d->pre, d->table0, d->tablek, d->theta, d->hout, d->hinit, d->hinit2, d->xbias, d->periph ? nullptr : d->ptab},
                              {d->x_sn, d->x ? d->x_sk : 0, d->periph ? d->p_sn : 0, d->periph ? d->p_sk : 0,
                               d->out ? d->o_sn : 0, d->out ? d->o_sk : 0});
     const int lanes = (d->D + vec - 1) / vec;
     if (lanes > 64) return fail(KPGNN_ELIMIT, "aggregate_fwd: D=%d with %d-wide access needs %d lanes > 64", d->D, vec, lanes);
-    const int g = pick_group(lanes);
     hipStream_t s = (hipStream_t)stream;
-#define KP_CALL(VEC_, G_) launch_fwd_mode<VEC_, G_>(p, tab, lds, s)
-    KP_DISPATCH_SHAPE(KP_CALL)
-#undef KP_CALL
-    return fail(KPGNN_EINVAL, "aggregate_fwd: no kernel for vec=%d g=%d", vec, g);
+    return dispatch_row_shape<64>(vec, row_lanes(d->D, vec), "aggregate_fwd",
+                                  [&](auto VV, auto G) { return launch_fwd_mode<VV.value, G.value>(p, tab, lds, s); });
 }
 
 extern "C" int kpgnn_aggregate_bwd(const kpgnn_agg_bwd_desc* d, kpgnn_stream_t stream) {
@@ -842,13 +786,10 @@ extern "C" int kpgnn_aggregate_bwd(const kpgnn_agg_bwd_desc* d, kpgnn_stream_t s
     }
     if ((uint64_t)d->N * (uint64_t)d->g_sn * 4u >= (1ull << 32))
         return fail(KPGNN_ELIMIT, "aggregate_bwd: N * g row stride = %lld floats exceeds the 32-bit byte offsets of the gather", (long long)d->N * d->g_sn);
-    const int vec = pick_vec(d->D, {d->g, d->gx ? (const void*)d->gx : slot_align}, {d->g_sn, d->g_sk, d->gx_sn, d->gx ? d->gx_sk : 0});
+    const int vec = row_vec(d->D, {d->g, d->gx ? (const void*)d->gx : slot_align}, {d->g_sn, d->g_sk, d->gx_sn, d->gx ? d->gx_sk : 0});
     const int lanes = (d->D + vec - 1) / vec;
     if (lanes > 64) return fail(KPGNN_ELIMIT, "aggregate_bwd: D=%d with %d-wide access needs %d lanes > 64", d->D, vec, lanes);
-    const int g = pick_group(lanes);
     hipStream_t s = (hipStream_t)stream;
-#define KP_CALL(VEC_, G_) launch_bwd_mode<VEC_, G_>(p, tab, lds, s)
-    KP_DISPATCH_SHAPE(KP_CALL)
-#undef KP_CALL
-    return fail(KPGNN_EINVAL, "aggregate_bwd: no kernel for vec=%d g=%d", vec, g);
+    return dispatch_row_shape<64>(vec, row_lanes(d->D, vec), "aggregate_bwd",
+                                  [&](auto VV, auto G) { return launch_bwd_mode<VV.value, G.value>(p, tab, lds, s); });
 }

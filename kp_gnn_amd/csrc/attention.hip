@@ -61,19 +61,6 @@ __global__ void __launch_bounds__(kBlock) attn_lstm_fwd_kernel(const AtParams p)
 }
 
 // ---- softmax over the slots + weighted sum: sub-group of G lanes per node, 16-B columns
-template <int VEC> struct VT;
-template <> struct VT<1> { using T = float; };
-template <> struct VT<4> { using T = float4; };
-template <int VEC> __device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
-    typename VT<VEC>::T t = *reinterpret_cast<const typename VT<VEC>::T*>(p);
-    for (int q = 0; q < VEC; ++q) v[q] = reinterpret_cast<const float*>(&t)[q];
-}
-template <int VEC> __device__ __forceinline__ void stv(float* p, const float (&v)[VEC]) {
-    typename VT<VEC>::T t;
-    for (int q = 0; q < VEC; ++q) reinterpret_cast<float*>(&t)[q] = v[q];
-    *reinterpret_cast<typename VT<VEC>::T*>(p) = t;
-}
-
 // (KMAX: the slots' rows of a node are requested together, before the softmax arithmetic - a load per loop iteration made the
 //  weighted sum a chain of K round trips per node)
 template <int G, int VEC, int KMAX>
@@ -614,17 +601,6 @@ __global__ void __launch_bounds__(256) attn_unpad_kernel(const float* dw_pad, co
         default: return fail(KPGNN_ELIMIT, "attention combine: K=%d > 16", K);                                   \
     }
 
-int apply_vec(const kpgnn_attn_desc* d) {
-    const bool v4 = d->D % 4 == 0 && (d->x_sn % 4) == 0 && (d->x_sk % 4) == 0 && (((uintptr_t)d->x) & 15) == 0 &&
-                    (((uintptr_t)d->out) & 15) == 0 && (((uintptr_t)d->gout) & 15) == 0 && (((uintptr_t)d->dx) & 15) == 0;
-    return v4 ? 4 : 1;
-}
-int apply_group(int D, int vec) {
-    int g = 4;
-    while (g * vec < D) g <<= 1;
-    return g;
-}
-
 int check(const kpgnn_attn_desc* d, bool bwd) {
     KPGNN_REQUIRE(d != nullptr, "attn: NULL descriptor");
     KPGNN_REQUIRE(d->N >= 0 && d->K >= 1 && d->D >= 1, "attn: bad N=%d K=%d D=%d", d->N, d->K, d->D);
@@ -642,43 +618,31 @@ void fill(const kpgnn_attn_desc* d, AtParams* p) {
     p->dgin = d->dgin; p->hprev = d->hprev;
 }
 
-int launch_apply_fwd(const kpgnn_attn_desc* d, const AtParams& p, hipStream_t s) {
+// the softmax + weighted sum (BWD: its backward) over rows of D columns.  These kernels are <G, VEC, KMAX> and exist for VEC 4
+// and 1 only: 4 columns per lane when everything allows it, else 1; the shared table gives G alone.
+template <bool BWD>
+int launch_apply(const kpgnn_attn_desc* d, const AtParams& p, hipStream_t s) {
     const int K = d->K;
-    dim3 blk(kBlock);
-    const int vec = apply_vec(d);
-    const int g = apply_group(d->D, vec);
+    const int vec = row_vec(d->D, {d->x, d->out, d->gout, d->dx}, {d->x_sn, d->x_sk}) == 4 ? 4 : 1;
+    const int g = row_lanes(d->D, vec);
     if (g > 64) return fail(KPGNN_ELIMIT, "attention combine: D=%d needs more than 64 lanes", d->D);
     int64_t nb = ((int64_t)d->N + (kBlock / g) - 1) / (kBlock / g);
     const int64_t cap = (int64_t)device_facts().cu_count * 8;
     if (nb > cap) nb = cap;
-#define KP_AP(GG) do { if (vec == 4 && K <= 8) hipLaunchKernelGGL((attn_apply_fwd_kernel<GG, 4, 8>), dim3((unsigned)nb), blk, 0, s, p, K); \
-                       else if (vec == 4) hipLaunchKernelGGL((attn_apply_fwd_kernel<GG, 4, 16>), dim3((unsigned)nb), blk, 0, s, p, K); \
-                       else if (K <= 8) hipLaunchKernelGGL((attn_apply_fwd_kernel<GG, 1, 8>), dim3((unsigned)nb), blk, 0, s, p, K); \
-                       else hipLaunchKernelGGL((attn_apply_fwd_kernel<GG, 1, 16>), dim3((unsigned)nb), blk, 0, s, p, K); } while (0)
-    switch (g) { case 4: KP_AP(4); break; case 8: KP_AP(8); break; case 16: KP_AP(16); break; case 32: KP_AP(32); break; default: KP_AP(64); break; }
-#undef KP_AP
-    KPGNN_LAUNCH_CHECK("attn_apply_fwd_kernel");
-    return KPGNN_OK;
+    return dispatch_row_lanes<64>(g, "attention combine", [&](auto G) {
+        void (*kernel)(const AtParams, int);
+        if constexpr (BWD) kernel = vec == 4 ? (K <= 8 ? attn_apply_bwd_kernel<G.value, 4, 8> : attn_apply_bwd_kernel<G.value, 4, 16>)
+                                             : (K <= 8 ? attn_apply_bwd_kernel<G.value, 1, 8> : attn_apply_bwd_kernel<G.value, 1, 16>);
+        else kernel = vec == 4 ? (K <= 8 ? attn_apply_fwd_kernel<G.value, 4, 8> : attn_apply_fwd_kernel<G.value, 4, 16>)
+                               : (K <= 8 ? attn_apply_fwd_kernel<G.value, 1, 8> : attn_apply_fwd_kernel<G.value, 1, 16>);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, p, K);
+        KPGNN_LAUNCH_CHECK(BWD ? "attn_apply_bwd_kernel" : "attn_apply_fwd_kernel");
+        return KPGNN_OK;
+    });
 }
-
-int launch_apply_bwd(const kpgnn_attn_desc* d, const AtParams& p, hipStream_t s) {
-    const int K = d->K;
-    dim3 blk(kBlock);
-    const int vec = apply_vec(d);
-    const int g = apply_group(d->D, vec);
-    if (g > 64) return fail(KPGNN_ELIMIT, "attention combine: D=%d needs more than 64 lanes", d->D);
-    int64_t nb = ((int64_t)d->N + (kBlock / g) - 1) / (kBlock / g);
-    const int64_t cap = (int64_t)device_facts().cu_count * 8;
-    if (nb > cap) nb = cap;
-#define KP_AP(GG) do { if (vec == 4 && K <= 8) hipLaunchKernelGGL((attn_apply_bwd_kernel<GG, 4, 8>), dim3((unsigned)nb), blk, 0, s, p, K); \
-                       else if (vec == 4) hipLaunchKernelGGL((attn_apply_bwd_kernel<GG, 4, 16>), dim3((unsigned)nb), blk, 0, s, p, K); \
-                       else if (K <= 8) hipLaunchKernelGGL((attn_apply_bwd_kernel<GG, 1, 8>), dim3((unsigned)nb), blk, 0, s, p, K); \
-                       else hipLaunchKernelGGL((attn_apply_bwd_kernel<GG, 1, 16>), dim3((unsigned)nb), blk, 0, s, p, K); } while (0)
-    switch (g) { case 4: KP_AP(4); break; case 8: KP_AP(8); break; case 16: KP_AP(16); break; case 32: KP_AP(32); break; default: KP_AP(64); break; }
-#undef KP_AP
-    KPGNN_LAUNCH_CHECK("attn_apply_bwd_kernel");
-    return KPGNN_OK;
-}
+// (instantiated here rather than at first use below: the apply kernels keep their place at the head of the code object)
+template int launch_apply<false>(const kpgnn_attn_desc*, const AtParams&, hipStream_t);
+template int launch_apply<true>(const kpgnn_attn_desc*, const AtParams&, hipStream_t);
 
 int check_scan(const kpgnn_attn_scan_desc* d, bool bwd) {
     KPGNN_REQUIRE(d != nullptr, "attn_scan: NULL descriptor");
@@ -724,7 +688,7 @@ extern "C" int kpgnn_attn_fwd(const kpgnn_attn_desc* d, kpgnn_stream_t stream) {
     dim3 grid((unsigned)((d->N + kBlock - 1) / kBlock), 2), blk(kBlock);
     KP_K_SWITCH(attn_lstm_fwd_kernel, grid, blk, s, p)
     KPGNN_LAUNCH_CHECK("attn_lstm_fwd_kernel");
-    return launch_apply_fwd(d, p, s);
+    return launch_apply<false>(d, p, s);
 }
 
 extern "C" int kpgnn_attn_bwd(const kpgnn_attn_desc* d, kpgnn_stream_t stream) {
@@ -735,7 +699,7 @@ extern "C" int kpgnn_attn_bwd(const kpgnn_attn_desc* d, kpgnn_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     const int K = d->K;
     dim3 blk(kBlock);
-    rc = launch_apply_bwd(d, p, s);
+    rc = launch_apply<true>(d, p, s);
     if (rc != KPGNN_OK) return rc;
     dim3 grid((unsigned)((d->N + kBlock - 1) / kBlock), 2);
     KP_K_SWITCH(attn_lstm_bwd_kernel, grid, blk, s, p)
@@ -758,7 +722,7 @@ extern "C" int kpgnn_attn_scan_fwd(const kpgnn_attn_scan_desc* d, kpgnn_stream_t
     else if (ks <= 7) hipLaunchKernelGGL(attn_scan_fwd_kernel<7>, grid, blk, 0, s, q);
     else hipLaunchKernelGGL(attn_scan_fwd_kernel<8>, grid, blk, 0, s, q);
     KPGNN_LAUNCH_CHECK("attn_scan_fwd_kernel");
-    return launch_apply_fwd(&a, p, s);
+    return launch_apply<false>(&a, p, s);
 }
 
 extern "C" int kpgnn_attn_scan_bwd(const kpgnn_attn_scan_desc* d, kpgnn_stream_t stream) {
@@ -769,7 +733,7 @@ extern "C" int kpgnn_attn_scan_bwd(const kpgnn_attn_scan_desc* d, kpgnn_stream_t
     fill_scan(d, &q, &p, &a);
     hipStream_t s = (hipStream_t)stream;
     p.dx = nullptr;                                    // ds only: the direct part of dx is the epilogue of attn_dx_kernel
-    rc = launch_apply_bwd(&a, p, s);
+    rc = launch_apply<true>(&a, p, s);
     if (rc != KPGNN_OK) return rc;
     const int ntiles = (d->N + 31) / 32;
     dim3 grid((unsigned)((ntiles + 1) / 2)), blk(kScanThreads);

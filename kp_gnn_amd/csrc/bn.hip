@@ -17,20 +17,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kProducerBlocks = 512;   // blocks of a launch that adds to a slot: 512 / 8 replicas = 64 adds per address
 
-template <int VEC> struct VT;
-template <> struct VT<1> { using T = float; };
-template <> struct VT<2> { using T = float2; };
-template <> struct VT<4> { using T = float4; };
-template <int VEC> __device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
-    typename VT<VEC>::T t = *reinterpret_cast<const typename VT<VEC>::T*>(p);
-    for (int q = 0; q < VEC; ++q) v[q] = reinterpret_cast<const float*>(&t)[q];
-}
-template <int VEC> __device__ __forceinline__ void stv(float* p, const float (&v)[VEC]) {
-    typename VT<VEC>::T t;
-    for (int q = 0; q < VEC; ++q) reinterpret_cast<float*>(&t)[q] = v[q];
-    *reinterpret_cast<typename VT<VEC>::T*>(p) = t;
-}
-
 struct BnParams {
     const int32_t* n_dyn;
     int64_t N; int C, relu; float eps, momentum;
@@ -49,13 +35,6 @@ struct BnParams {
     // stacked forward: the outer norm
     const float* og; const float* ob; float oeps, omom; float* ormean; float* orvar; int64_t* onbt; float* omean; float* oinvstd;
 };
-
-__device__ __forceinline__ double slot_sum(const double* slot, int C, int which, int c) {
-    double s = 0.0;
-#pragma unroll
-    for (int r = 0; r < KPGNN_STAT_REPLICAS; ++r) s += slot[((int64_t)r * 2 + which) * C + c];
-    return s;
-}
 
 // Block reduction of per-thread (a,b)[VEC] over the row lanes (fixed order), then 2C fp64 atomics into this block's replica.
 template <int VEC, int G>
@@ -434,14 +413,10 @@ __global__ void __launch_bounds__(kBlock) bn_bwd_apply_kernel(BnParams p) {
 }
 
 int bn_shape(int C, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> strides, int* vec, int* g) {
-    int v = (C % 4 == 0) ? 4 : (C % 2 == 0 ? 2 : 1);
-    for (const void* q : ptrs) while (v > 1 && q && ((uintptr_t)q % (v * 4))) v >>= 1;
-    for (int64_t s : strides) while (v > 1 && (s % v)) v >>= 1;
-    const int lanes = (C + v - 1) / v;
+    *vec = row_vec(C, ptrs, strides);
+    const int lanes = (C + *vec - 1) / *vec;
     if (lanes > 64) return fail(KPGNN_ELIMIT, "batch norm: C=%d needs %d lanes > 64 (C <= 256)", C, lanes);
-    int gg = 4;
-    while (gg < lanes) gg <<= 1;
-    *vec = v; *g = gg;
+    *g = row_lanes(C, *vec);
     return KPGNN_OK;
 }
 
@@ -452,18 +427,14 @@ int stream_grid(int64_t N, int G, int cap_blocks) {
     return (int)(g < 1 ? 1 : g);
 }
 
-#define KP_BN_CASE(KERNEL, V, GG, GRID) case V * 100 + GG: hipLaunchKernelGGL((KERNEL<V, GG>), dim3(GRID), dim3(kBlock), 0, s, p); break;
-#define KP_BN_SWITCH(KERNEL, GRID)                                                                                   \
-    switch (vec * 100 + g) {                                                                                         \
-        KP_BN_CASE(KERNEL, 4, 4, GRID) KP_BN_CASE(KERNEL, 4, 8, GRID) KP_BN_CASE(KERNEL, 4, 16, GRID)                \
-        KP_BN_CASE(KERNEL, 4, 32, GRID) KP_BN_CASE(KERNEL, 4, 64, GRID)                                              \
-        KP_BN_CASE(KERNEL, 2, 4, GRID) KP_BN_CASE(KERNEL, 2, 8, GRID) KP_BN_CASE(KERNEL, 2, 16, GRID)                \
-        KP_BN_CASE(KERNEL, 2, 32, GRID) KP_BN_CASE(KERNEL, 2, 64, GRID)                                              \
-        KP_BN_CASE(KERNEL, 1, 4, GRID) KP_BN_CASE(KERNEL, 1, 8, GRID) KP_BN_CASE(KERNEL, 1, 16, GRID)                \
-        KP_BN_CASE(KERNEL, 1, 32, GRID) KP_BN_CASE(KERNEL, 1, 64, GRID)                                              \
-        default: return fail(KPGNN_EINVAL, "batch norm: no kernel for vec=%d g=%d", vec, g);                         \
-    }                                                                                                                \
-    KPGNN_LAUNCH_CHECK(#KERNEL)
+// KERNEL<vec, g, extra template arguments...> on GRID blocks
+#define KP_BN_LAUNCH(KERNEL, GRID, ...)                                                                              \
+    rc = dispatch_row_shape<64>(vec, g, "batch norm", [&](auto V, auto GG) {                                         \
+        hipLaunchKernelGGL((KERNEL<V.value, GG.value, ##__VA_ARGS__>), dim3(GRID), dim3(kBlock), 0, s, p);           \
+        KPGNN_LAUNCH_CHECK(#KERNEL);                                                                                 \
+        return KPGNN_OK;                                                                                             \
+    });                                                                                                              \
+    if (rc != KPGNN_OK) return rc
 
 }  // namespace
 }  // namespace kpgnn
@@ -498,42 +469,29 @@ extern "C" int kpgnn_bn_fwd(const kpgnn_bn_desc* d, kpgnn_stream_t stream) {
         }
         p.in_slot = d->stat_slot; p.out_slot = d->out_slot;
         const int nstat = stream_grid(d->N, g, kProducerBlocks);
-        KP_BN_SWITCH(bn_act_stats_kernel, nstat);
+        KP_BN_LAUNCH(bn_act_stats_kernel, nstat);
         p.in_slot = d->out_slot; p.out_slot = nullptr;
         p.og = d->outer_gamma; p.ob = d->outer_beta; p.oeps = d->outer_eps; p.omom = d->outer_momentum;
         p.ormean = d->outer_running_mean; p.orvar = d->outer_running_var; p.onbt = d->outer_num_batches_tracked;
         p.omean = d->outer_mean; p.oinvstd = d->outer_invstd;
         const int napply = stream_grid(d->N, g, device_facts().cu_count * 8);
-        KP_BN_SWITCH(bn_apply2_kernel, napply);
+        KP_BN_LAUNCH(bn_apply2_kernel, napply);
         return KPGNN_OK;
     }
     if (!d->stats_ready) {
         p.out_slot = d->stat_slot;
         const int nstat = stream_grid(d->N, g, kProducerBlocks);
-        KP_BN_SWITCH(bn_stats_kernel, nstat);
+        KP_BN_LAUNCH(bn_stats_kernel, nstat);
     }
     p.in_slot = d->stat_slot;
     p.out_slot = d->out_slot;
     if (d->out_slot) {
         const int napply = stream_grid(d->N, g, kProducerBlocks);
-        switch (vec * 100 + g) {
-#define KP_C(V, GG) case V * 100 + GG: hipLaunchKernelGGL((bn_apply_kernel<V, GG, true>), dim3(napply), dim3(kBlock), 0, s, p); break;
-            KP_C(4, 4) KP_C(4, 8) KP_C(4, 16) KP_C(4, 32) KP_C(4, 64) KP_C(2, 4) KP_C(2, 8) KP_C(2, 16) KP_C(2, 32) KP_C(2, 64)
-            KP_C(1, 4) KP_C(1, 8) KP_C(1, 16) KP_C(1, 32) KP_C(1, 64)
-#undef KP_C
-            default: return fail(KPGNN_EINVAL, "batch norm: no kernel for vec=%d g=%d", vec, g);
-        }
+        KP_BN_LAUNCH(bn_apply_kernel, napply, true);
     } else {
         const int napply = stream_grid(d->N, g, device_facts().cu_count * 8);
-        switch (vec * 100 + g) {
-#define KP_C(V, GG) case V * 100 + GG: hipLaunchKernelGGL((bn_apply_kernel<V, GG, false>), dim3(napply), dim3(kBlock), 0, s, p); break;
-            KP_C(4, 4) KP_C(4, 8) KP_C(4, 16) KP_C(4, 32) KP_C(4, 64) KP_C(2, 4) KP_C(2, 8) KP_C(2, 16) KP_C(2, 32) KP_C(2, 64)
-            KP_C(1, 4) KP_C(1, 8) KP_C(1, 16) KP_C(1, 32) KP_C(1, 64)
-#undef KP_C
-            default: return fail(KPGNN_EINVAL, "batch norm: no kernel for vec=%d g=%d", vec, g);
-        }
+        KP_BN_LAUNCH(bn_apply_kernel, napply, false);
     }
-    KPGNN_LAUNCH_CHECK("bn_apply_kernel");
     return KPGNN_OK;
 }
 
@@ -560,12 +518,12 @@ extern "C" int kpgnn_bn_bwd(const kpgnn_bn_bwd_desc* d, kpgnn_stream_t stream) {
     if (d->outer_mean) {
         KPGNN_REQUIRE(d->reduce_only && d->outer_invstd, "bn_bwd: the stacked reduce (outer_mean) needs reduce_only and outer_invstd");
         p.o_mean = d->outer_mean; p.o_invstd = d->outer_invstd;
-        KP_BN_SWITCH(bn_bwd_reduce2_kernel, nstat);
+        KP_BN_LAUNCH(bn_bwd_reduce2_kernel, nstat);
         return KPGNN_OK;
     }
-    KP_BN_SWITCH(bn_bwd_reduce_kernel, nstat);
+    KP_BN_LAUNCH(bn_bwd_reduce_kernel, nstat);
     if (d->reduce_only) return KPGNN_OK;
     const int napply = stream_grid(d->N, g, device_facts().cu_count * 8);
-    KP_BN_SWITCH(bn_bwd_apply_kernel, napply);
+    KP_BN_LAUNCH(bn_bwd_apply_kernel, napply);
     return KPGNN_OK;
 }

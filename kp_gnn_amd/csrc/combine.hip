@@ -15,24 +15,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-template <int VEC> struct VT;
-template <> struct VT<1> { using T = float; };
-template <> struct VT<2> { using T = float2; };
-template <> struct VT<4> { using T = float4; };
-
-template <int VEC> __device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
-    typename VT<VEC>::T t = *reinterpret_cast<const typename VT<VEC>::T*>(p);
-    for (int q = 0; q < VEC; ++q) v[q] = reinterpret_cast<const float*>(&t)[q];
-}
-template <int VEC> __device__ __forceinline__ void ldv_stream(const float* p, float (&v)[VEC]) {   // read-once stream (nt)
-    for (int q = 0; q < VEC; ++q) v[q] = __builtin_nontemporal_load(p + q);
-}
-template <int VEC> __device__ __forceinline__ void stv(float* p, const float (&v)[VEC]) {
-    typename VT<VEC>::T t;
-    for (int q = 0; q < VEC; ++q) reinterpret_cast<float*>(&t)[q] = v[q];
-    *reinterpret_cast<typename VT<VEC>::T*>(p) = t;
-}
-
 struct CbParams {
     int N, K, D, mode;
     const float* pre;
@@ -177,16 +159,11 @@ int cb_grid(int N, int K, int G, int per_cu) {
 }
 
 int cb_shape(const kpgnn_combine_bwd_desc* d, int* vec, int* g) {
-    int v = (d->D % 4 == 0) ? 4 : (d->D % 2 == 0 ? 2 : 1);
-    auto al = [&](const void* q) { while (v > 1 && q && ((uintptr_t)q % (v * 4))) v >>= 1; };
-    al(d->pre); al(d->gh); al(d->theta); al(d->gout); al(d->periph); al(d->ptab); al(d->g); al(d->gv);
-    for (int64_t s : {d->gout ? d->go_sn : 0, d->gout ? d->go_sk : 0, d->periph ? d->p_sn : 0, d->periph ? d->p_sk : 0})
-        while (v > 1 && (s % v)) v >>= 1;
-    const int lanes = (d->D + v - 1) / v;
+    *vec = row_vec(d->D, {d->pre, d->gh, d->theta, d->gout, d->periph, d->ptab, d->g, d->gv},
+                   {d->gout ? d->go_sn : 0, d->gout ? d->go_sk : 0, d->periph ? d->p_sn : 0, d->periph ? d->p_sk : 0});
+    const int lanes = (d->D + *vec - 1) / *vec;
     if (lanes > 64) return fail(KPGNN_ELIMIT, "combine_bwd: D=%d needs %d lanes > 64", d->D, lanes);
-    int gg = 4;
-    while (gg < lanes) gg <<= 1;
-    *vec = v; *g = gg;
+    *g = row_lanes(d->D, *vec);
     return KPGNN_OK;
 }
 
@@ -259,14 +236,7 @@ extern "C" int kpgnn_combine_bwd(const kpgnn_combine_bwd_desc* d, kpgnn_stream_t
         if (p.ptab && p.uid && d->n_dict > 0 && (size_t)d->n_dict * d->D * sizeof(float) <= 16 * 1024) p.lds_ptab = d->n_dict * d->D;
     }
     hipStream_t s = (hipStream_t)stream;
-#define KP_CB(V, GG) rc = cb_launch<V, GG>(p, &grid, s); break
-    switch (vec * 100 + g) {
-        case 404: KP_CB(4, 4); case 408: KP_CB(4, 8); case 416: KP_CB(4, 16); case 432: KP_CB(4, 32); case 464: KP_CB(4, 64);
-        case 204: KP_CB(2, 4); case 208: KP_CB(2, 8); case 216: KP_CB(2, 16); case 232: KP_CB(2, 32); case 264: KP_CB(2, 64);
-        case 104: KP_CB(1, 4); case 108: KP_CB(1, 8); case 116: KP_CB(1, 16); case 132: KP_CB(1, 32); case 164: KP_CB(1, 64);
-        default: return fail(KPGNN_EINVAL, "combine_bwd: no kernel for vec=%d g=%d", vec, g);
-    }
-#undef KP_CB
+    rc = dispatch_row_shape<64>(vec, g, "combine_bwd", [&](auto V, auto G) { return cb_launch<V.value, G.value>(p, &grid, s); });
     if (rc != KPGNN_OK) return rc;
     if (p.slab && d->alphas && d->galphas)    // geometric combine: the finishing launch also differentiates theta(alphas)
         return gtheta_finish_launch(p.slab, grid, d->alphas, d->theta, d->K, d->D, d->gtheta, d->galphas, s);

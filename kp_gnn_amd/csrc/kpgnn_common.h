@@ -5,6 +5,8 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
+#include <type_traits>
 
 #include "kpgnn.h"
 
@@ -178,6 +180,32 @@ __device__ __forceinline__ float fast_erf(float z, float* e2_out) {
     return copysignf(fmaf(-poly * t, e2, 1.0f), z);
 }
 
+// VEC fp32 columns of a row as ONE 4 / 8 / 16-byte access (the address must be aligned to it: row_vec below decides VEC)
+template <int VEC> struct VT;
+template <> struct VT<1> { using T = float; };
+template <> struct VT<2> { using T = float2; };
+template <> struct VT<4> { using T = float4; };
+template <int VEC> __device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
+    typename VT<VEC>::T t = *reinterpret_cast<const typename VT<VEC>::T*>(p);
+    for (int q = 0; q < VEC; ++q) v[q] = reinterpret_cast<const float*>(&t)[q];
+}
+template <int VEC> __device__ __forceinline__ void ldv_stream(const float* p, float (&v)[VEC]) {   // read-once stream (nt)
+    for (int q = 0; q < VEC; ++q) v[q] = __builtin_nontemporal_load(p + q);
+}
+template <int VEC> __device__ __forceinline__ void stv(float* p, const float (&v)[VEC]) {
+    typename VT<VEC>::T t;
+    for (int q = 0; q < VEC; ++q) reinterpret_cast<float*>(&t)[q] = v[q];
+    *reinterpret_cast<typename VT<VEC>::T*>(p) = t;
+}
+
+// sum of the replicas of one column-statistics slot entry (kpgnn.h, "Column-statistics slots")
+__device__ __forceinline__ double slot_sum(const double* slot, int C, int which, int c) {
+    double s = 0.0;
+#pragma unroll
+    for (int r = 0; r < KPGNN_STAT_REPLICAS; ++r) s += slot[((int64_t)r * 2 + which) * C + c];
+    return s;
+}
+
 // bf16 STORAGE of rows that are otherwise fp32 (kpgnn.h: `storage` = KPGNN_STORE_BF16): the value is the upper half of the
 // fp32 pattern, rounded to nearest even on the way out; every sum stays fp32.
 __device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {
@@ -273,5 +301,44 @@ int resident_blocks(Kernel kernel, int block_threads, size_t lds) {
     return nb;
 }
 
+// ---- Row shape of the row-streaming kernels, templates over <VEC, G>: a sub-group of G lanes owns a row of D fp32 columns,
+// VEC of them per lane.  Host side; every launcher picks and dispatches the pair here.
+// VEC: the widest of 4 / 2 / 1 that divides D and every row stride (in floats) and keeps every pointer 4 * VEC-byte
+// aligned.  NULL pointers and zero strides (operands a call does not use) constrain nothing.
+inline int row_vec(int D, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> strides) {
+    int v = (D % 4 == 0) ? 4 : (D % 2 == 0 ? 2 : 1);
+    for (const void* q : ptrs) while (v > 1 && ((uintptr_t)q % (v * 4))) v >>= 1;
+    for (int64_t s : strides) while (v > 1 && (s % v)) v >>= 1;
+    return v;
+}
+// G: the power of two >= max(4, ceil(D / vec)).  The caller bounds D first: its own lane limit, its own KPGNN_ELIMIT text.
+inline int row_lanes(int D, int vec) {
+    int g = 4;
+    while (g * vec < D) g <<= 1;
+    return g;
+}
+// The one table of instantiated pairs: G = 4 .. 64 for every VEC, and up to MAXG where G * VEC <= 256 (pool.hip alone).
+// f(std::integral_constant<int, VEC>, std::integral_constant<int, G>) launches its kernel<VEC, G> and returns the status.
+template <int MAXG, typename F>
+int dispatch_row_shape(int vec, int g, const char* who, F&& f) {
+#define KPGNN_ROW_CASE(V, G)                                                                                          \
+    case V * 1000 + G:                                                                                                \
+        if constexpr (G <= MAXG) return f(std::integral_constant<int, V>{}, std::integral_constant<int, G>{});        \
+        else break;
+    switch (vec * 1000 + g) {
+        KPGNN_ROW_CASE(4, 4) KPGNN_ROW_CASE(4, 8) KPGNN_ROW_CASE(4, 16) KPGNN_ROW_CASE(4, 32) KPGNN_ROW_CASE(4, 64)
+        KPGNN_ROW_CASE(2, 4) KPGNN_ROW_CASE(2, 8) KPGNN_ROW_CASE(2, 16) KPGNN_ROW_CASE(2, 32) KPGNN_ROW_CASE(2, 64)
+        KPGNN_ROW_CASE(2, 128)
+        KPGNN_ROW_CASE(1, 4) KPGNN_ROW_CASE(1, 8) KPGNN_ROW_CASE(1, 16) KPGNN_ROW_CASE(1, 32) KPGNN_ROW_CASE(1, 64)
+        KPGNN_ROW_CASE(1, 128) KPGNN_ROW_CASE(1, 256)
+    }
+#undef KPGNN_ROW_CASE
+    return fail(KPGNN_EINVAL, "%s: no kernel for vec=%d g=%d", who, vec, g);
+}
+// G alone from the same table, for kernels whose VEC is not this table's business: f(std::integral_constant<int, G>)
+template <int MAXG, typename F>
+int dispatch_row_lanes(int g, const char* who, F&& f) {
+    return dispatch_row_shape<MAXG>(1, g, who, [&](auto, auto G) { return f(G); });
+}
 
 }  // namespace kpgnn

@@ -61,14 +61,6 @@ struct LinFParams {
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
 
-// sum of the replicas of one slot entry
-__device__ __forceinline__ double slot_sum(const double* slot, int C, int which, int c) {
-    double s = 0.0;
-#pragma unroll
-    for (int r = 0; r < KPGNN_STAT_REPLICAS; ++r) s += slot[((int64_t)r * 2 + which) * C + c];
-    return s;
-}
-
 template <int KS, int M, int PRO, int EPI>
 __global__ void __launch_bounds__(256, 2)
 lin_fused_kernel(LinFParams p) {

@@ -13,20 +13,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-template <int VEC> struct VT;
-template <> struct VT<1> { using T = float; };
-template <> struct VT<2> { using T = float2; };
-template <> struct VT<4> { using T = float4; };
-template <int VEC> __device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
-    typename VT<VEC>::T t = *reinterpret_cast<const typename VT<VEC>::T*>(p);
-    for (int q = 0; q < VEC; ++q) v[q] = reinterpret_cast<const float*>(&t)[q];
-}
-template <int VEC> __device__ __forceinline__ void stv(float* p, const float (&v)[VEC]) {
-    typename VT<VEC>::T t;
-    for (int q = 0; q < VEC; ++q) reinterpret_cast<float*>(&t)[q] = v[q];
-    *reinterpret_cast<typename VT<VEC>::T*>(p) = t;
-}
-
 struct PoolParams {
     const int32_t* n_dyn;
     int64_t N; int G, D, mean;
@@ -81,40 +67,18 @@ __global__ void __launch_bounds__(kBlock) pool_bwd_kernel(PoolParams p) {
 }
 
 int shape(int D, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> strides, int* vec, int* lanes) {
-    int v = (D % 4 == 0) ? 4 : (D % 2 == 0 ? 2 : 1);
-    for (const void* q : ptrs) while (v > 1 && q && ((uintptr_t)q % (v * 4))) v >>= 1;
-    for (int64_t s : strides) while (v > 1 && (s % v)) v >>= 1;
-    const int need = (D + v - 1) / v;
-    if (need > 256) return fail(KPGNN_ELIMIT, "segment_pool: D=%d too wide", D);
-    int l = 4;
-    while (l < need) l <<= 1;
-    *vec = v; *lanes = l;
+    *vec = row_vec(D, ptrs, strides);
+    if ((D + *vec - 1) / *vec > 256) return fail(KPGNN_ELIMIT, "segment_pool: D=%d too wide", D);
+    *lanes = row_lanes(D, *vec);
     return KPGNN_OK;
 }
 
-#define KP_POOL_SWITCH(KERNEL, GRID)                                                                         \
-    switch (vec * 1000 + lanes) {                                                                            \
-        case 4004: hipLaunchKernelGGL((KERNEL<4, 4>), dim3(GRID), dim3(kBlock), 0, s, p); break;             \
-        case 4008: hipLaunchKernelGGL((KERNEL<4, 8>), dim3(GRID), dim3(kBlock), 0, s, p); break;             \
-        case 4016: hipLaunchKernelGGL((KERNEL<4, 16>), dim3(GRID), dim3(kBlock), 0, s, p); break;            \
-        case 4032: hipLaunchKernelGGL((KERNEL<4, 32>), dim3(GRID), dim3(kBlock), 0, s, p); break;            \
-        case 4064: hipLaunchKernelGGL((KERNEL<4, 64>), dim3(GRID), dim3(kBlock), 0, s, p); break;            \
-        case 2004: hipLaunchKernelGGL((KERNEL<2, 4>), dim3(GRID), dim3(kBlock), 0, s, p); break;             \
-        case 2008: hipLaunchKernelGGL((KERNEL<2, 8>), dim3(GRID), dim3(kBlock), 0, s, p); break;             \
-        case 2016: hipLaunchKernelGGL((KERNEL<2, 16>), dim3(GRID), dim3(kBlock), 0, s, p); break;            \
-        case 2032: hipLaunchKernelGGL((KERNEL<2, 32>), dim3(GRID), dim3(kBlock), 0, s, p); break;            \
-        case 2064: hipLaunchKernelGGL((KERNEL<2, 64>), dim3(GRID), dim3(kBlock), 0, s, p); break;            \
-        case 2128: hipLaunchKernelGGL((KERNEL<2, 128>), dim3(GRID), dim3(kBlock), 0, s, p); break;           \
-        case 1004: hipLaunchKernelGGL((KERNEL<1, 4>), dim3(GRID), dim3(kBlock), 0, s, p); break;             \
-        case 1008: hipLaunchKernelGGL((KERNEL<1, 8>), dim3(GRID), dim3(kBlock), 0, s, p); break;             \
-        case 1016: hipLaunchKernelGGL((KERNEL<1, 16>), dim3(GRID), dim3(kBlock), 0, s, p); break;            \
-        case 1032: hipLaunchKernelGGL((KERNEL<1, 32>), dim3(GRID), dim3(kBlock), 0, s, p); break;            \
-        case 1064: hipLaunchKernelGGL((KERNEL<1, 64>), dim3(GRID), dim3(kBlock), 0, s, p); break;            \
-        case 1128: hipLaunchKernelGGL((KERNEL<1, 128>), dim3(GRID), dim3(kBlock), 0, s, p); break;           \
-        case 1256: hipLaunchKernelGGL((KERNEL<1, 256>), dim3(GRID), dim3(kBlock), 0, s, p); break;           \
-        default: return fail(KPGNN_EINVAL, "segment_pool: no kernel for vec=%d lanes=%d", vec, lanes);       \
-    }                                                                                                        \
-    KPGNN_LAUNCH_CHECK(#KERNEL)
+#define KP_POOL_LAUNCH(KERNEL, GRID)                                                                         \
+    return dispatch_row_shape<256>(vec, lanes, "segment_pool", [&](auto V, auto L) {                         \
+        hipLaunchKernelGGL((KERNEL<V.value, L.value>), dim3(GRID), dim3(kBlock), 0, s, p);                   \
+        KPGNN_LAUNCH_CHECK(#KERNEL);                                                                         \
+        return KPGNN_OK;                                                                                     \
+    })
 
 int check(const kpgnn_pool_desc* d, const char* who) {
     KPGNN_REQUIRE(d != nullptr, "%s: NULL descriptor", who);
@@ -141,8 +105,7 @@ extern "C" int kpgnn_segment_pool_fwd(const kpgnn_pool_desc* d, kpgnn_stream_t s
     p.N = d->N; p.n_dyn = d->n_dyn; p.G = d->G; p.D = d->D; p.mean = d->mode; p.ptr = d->graph_ptr; p.x = d->x; p.xs = d->x_stride; p.out = d->out;
     hipStream_t s = (hipStream_t)stream;
     const unsigned grid = (unsigned)((d->G + (kBlock / lanes) - 1) / (kBlock / lanes));
-    KP_POOL_SWITCH(pool_fwd_kernel, grid);
-    return KPGNN_OK;
+    KP_POOL_LAUNCH(pool_fwd_kernel, grid);
 }
 
 extern "C" int kpgnn_segment_pool_bwd(const kpgnn_pool_desc* d, kpgnn_stream_t stream) {
@@ -161,6 +124,5 @@ extern "C" int kpgnn_segment_pool_bwd(const kpgnn_pool_desc* d, kpgnn_stream_t s
     int64_t g = (d->N + rows * 4 - 1) / (rows * 4);
     const int64_t cap = (int64_t)device_facts().cu_count * 8;
     const unsigned grid = (unsigned)(g > cap ? cap : (g < 1 ? 1 : g));
-    KP_POOL_SWITCH(pool_bwd_kernel, grid);
-    return KPGNN_OK;
+    KP_POOL_LAUNCH(pool_bwd_kernel, grid);
 }

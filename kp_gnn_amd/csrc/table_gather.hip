@@ -18,11 +18,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr size_t kMaxLds = 96 * 1024;
 
-template <int VEC> struct VT;
-template <> struct VT<1> { using T = float; };
-template <> struct VT<2> { using T = float2; };
-template <> struct VT<4> { using T = float4; };
-
 struct TgsParams {
     const int32_t* n_dyn;
     int64_t M;
@@ -411,17 +406,12 @@ int run(const kpgnn_tgs_desc* d, hipStream_t s) {
         return KPGNN_OK;
     }
     // column splits: the fewest such that the LDS slice fits and the slice width stays VEC-aligned
-    const float* data = bwd ? d->gout : d->out;
-    const int64_t stride = bwd ? d->gout_stride : d->out_stride;
     int splits = 0, Ds = 0, vec = 1;
     for (int sct = 1; sct <= d->D; ++sct) {
         if (d->D % sct) continue;
         const int w = d->D / sct;
         if ((size_t)d->R * w * sizeof(float) > kMaxLds) continue;
-        int v = (w % 4 == 0) ? 4 : (w % 2 == 0 ? 2 : 1);
-        while (v > 1 && (((uintptr_t)data % (v * 4)) || (stride % v) ||
-                         (!bwd && d->bias && ((uintptr_t)d->bias % (v * 4)))))
-            v >>= 1;
+        const int v = row_vec(w, {d->out, d->bias}, {d->out_stride});
         if ((w + v - 1) / v > 64) continue;
         splits = sct; Ds = w; vec = v;
         break;
@@ -432,19 +422,8 @@ int run(const kpgnn_tgs_desc* d, hipStream_t s) {
     p.table = d->table; p.bias = d->bias; p.out = d->out; p.out_stride = d->out_stride;
     p.gout = d->gout; p.gout_stride = d->gout_stride; p.gtable = d->gtable;
     const size_t lds = (size_t)d->R * Ds * sizeof(float);
-    int g = 4;
-    while (g * vec < Ds) g <<= 1;
-#define KP_TGS(V, GG) launch<V, GG>(p, splits, lds, s)
-    switch (vec * 100 + g) {
-        case 404: return KP_TGS(4, 4); case 408: return KP_TGS(4, 8); case 416: return KP_TGS(4, 16);
-        case 432: return KP_TGS(4, 32); case 464: return KP_TGS(4, 64);
-        case 204: return KP_TGS(2, 4); case 208: return KP_TGS(2, 8); case 216: return KP_TGS(2, 16);
-        case 232: return KP_TGS(2, 32); case 264: return KP_TGS(2, 64);
-        case 104: return KP_TGS(1, 4); case 108: return KP_TGS(1, 8); case 116: return KP_TGS(1, 16);
-        case 132: return KP_TGS(1, 32); case 164: return KP_TGS(1, 64);
-    }
-#undef KP_TGS
-    return fail(KPGNN_EINVAL, "table_gather_sum: no kernel for vec=%d g=%d", vec, g);
+    return dispatch_row_shape<64>(vec, row_lanes(Ds, vec), "table_gather_sum",
+                                  [&](auto V, auto G) { return launch<V.value, G.value>(p, splits, lds, s); });
 }
 
 }  // namespace

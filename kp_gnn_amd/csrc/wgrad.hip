@@ -392,17 +392,6 @@ constexpr int kW3Pitch = 40;      // bf16 per staged column: 32 rows + 8 of padd
 // the fp32 kernel, 120 against 191 for nine problems (the jumping-knowledge projection); the operands' HBM time is 16 / 40 us.
 constexpr int kW3Blocks = 256;    // one 8-wave block per CU
 
-typedef __attribute__((ext_vector_type(2))) float bf3_f2;
-typedef __attribute__((ext_vector_type(2))) uint32_t bf3_u2;
-
-// three-way split of two values at once (packed subtracts): word pairs whose top halves are the bf16 pieces
-__device__ __forceinline__ void bf3_split2(const bf3_f2 v, bf3_u2& h, bf3_u2& m, bf3_u2& l) {
-    h = __builtin_bit_cast(bf3_u2, v) & 0xffff0000u;
-    const bf3_f2 r1 = v - __builtin_bit_cast(bf3_f2, h);
-    m = __builtin_bit_cast(bf3_u2, r1) & 0xffff0000u;
-    l = __builtin_bit_cast(bf3_u2, r1 - __builtin_bit_cast(bf3_f2, m));
-}
-
 template <int TI, bool MASK>
 __global__ void __launch_bounds__(512, 1)
 wgrad3_kernel(const Wg2Args A) {

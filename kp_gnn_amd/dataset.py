@@ -361,7 +361,6 @@ class KHopDataset:
         and readout offsets are already in place: no layer call, encoder or readout pays a build or a host sync for it.
         `edge_index` / `edge_attr` of the result are zero-length HANDLES ([2,0] / [0,K]): the layers only use them to find
         the attached CSR (and to slice the hop prefix `edge_attr[:, :k]`), the [E]-sized int64 tensors are never made."""
-        lib = _lib.load()
         dev = self.device
         hdr_h, B, N, A, n_ent = self.plan(ids)
         with torch.cuda.device(dev):
@@ -370,7 +369,7 @@ class KHopDataset:
             c.E = int(self.h_edges[hdr_h[:B]].sum())
             hp = self.h_hop_pairs[hdr_h[:B]].sum(0)
             c._apairs = {k + 1: int(hp[k]) for k in range(self.K - 1)}
-            _lib.check(lib.kpgnn_collate(ctypes.byref(d), torch.cuda.current_stream(dev).cuda_stream), "kpgnn_collate")
+            _lib.launch("kpgnn_collate", dev, ctypes.byref(d))
         out.num_khop_edges = c.E
         return out
 
@@ -437,9 +436,7 @@ class StaticBatch:
 
     def launch_collate(self):
         """Device side: kpgnn_collate into the static buffers (capturable: its arguments never change)."""
-        dev = self.ds.device
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().kpgnn_collate(ctypes.byref(self._desc), torch.cuda.current_stream(dev).cuda_stream), "kpgnn_collate")
+        _lib.launch("kpgnn_collate", self.ds.device, ctypes.byref(self._desc))
 
 
 def _zero_pe(dev, width, n):

@@ -70,8 +70,7 @@ def copy_grads(views, grads):
     dst = (ctypes.c_void_p * n)(*[v.data_ptr() for v, _ in fast])
     cnt = (ctypes.c_int64 * n)(*[v.numel() for v, _ in fast])
     dev = fast[0][0].device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().kpgnn_multi_copy(n, src, dst, cnt, torch.cuda.current_stream(dev).cuda_stream), "kpgnn_multi_copy")
+    _lib.launch("kpgnn_multi_copy", dev, n, src, dst, cnt)
 
 
 class FlatAdam:
@@ -100,18 +99,15 @@ class FlatAdam:
         invalidate_splits()       # (the launch below changes the weights without bumping their version counters)
         dev = self.param.device
         if self.state is not None:
-            with torch.cuda.device(dev):
-                _lib.check(_lib.load().kpgnn_adam_step_device(
-                    self.param.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                    self.param.numel(), self.state.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
-                    self.weight_decay, torch.cuda.current_stream(dev).cuda_stream), "kpgnn_adam_step_device")
+            _lib.launch("kpgnn_adam_step_device", dev,
+                        self.param.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                        self.param.numel(), self.state.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
+                        self.weight_decay)
             return
         self.steps += 1
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().kpgnn_adam_step(
-                self.param.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                self.param.numel(), self.steps, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
-                torch.cuda.current_stream(dev).cuda_stream), "kpgnn_adam_step")
+        _lib.launch("kpgnn_adam_step", dev,
+                    self.param.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                    self.param.numel(), self.steps, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay)
 
 
 def allreduce_mean(flat, world):

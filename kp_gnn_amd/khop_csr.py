@@ -51,10 +51,8 @@ class KHopCSR:
             optr = torch.empty_like(self.tile_ptr)
             opack = torch.empty_like(self.tile_pack)
             scratch = torch.empty(max(ntiles, 1), dtype=torch.int32, device=self.tile_ptr.device)
-            with torch.cuda.device(self.tile_ptr.device):
-                _lib.check(_lib.load().kpgnn_tile_pack_filter(
-                    self.tile_ptr.data_ptr(), self.tile_pack.data_ptr(), ntiles, k_active, optr.data_ptr(), opack.data_ptr(),
-                    scratch.data_ptr(), torch.cuda.current_stream().cuda_stream), "kpgnn_tile_pack_filter")
+            _lib.launch("kpgnn_tile_pack_filter", self.tile_ptr.device, self.tile_ptr.data_ptr(), self.tile_pack.data_ptr(), ntiles,
+                        k_active, optr.data_ptr(), opack.data_ptr(), scratch.data_ptr())
             hit = self._tile_lists[k_active] = (optr, opack)
         return hit
 
@@ -109,43 +107,39 @@ class KHopCSR:
             raise ValueError(f"edge_index {tuple(edge_index.shape)} does not match edge_attr {tuple(edge_attr.shape)}")
         N = int(num_nodes)
         dev = edge_index.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
         ei_stride = edge_index.stride(0) if E > 0 else max(E, 1)
         at_stride = edge_attr.stride(0) if E > 0 else K
         stats = torch.empty(8, dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_csr_stats(edge_index.data_ptr(), ei_stride, edge_attr.data_ptr(), at_stride, E, K,
-                                           stats.data_ptr(), stream), "kpgnn_csr_stats")
-            A, max0, maxk, minv, nmin, nmax = stats.tolist()[:6]  # the one host sync of a batch build
-            if minv < 0:
-                raise ValueError("edge_attr holds negative codes")
-            if E > 0 and (nmin < 0 or nmax >= N):
-                raise IndexError(f"edge_index out of range [0, {N}): min {nmin}, max {nmax}")
-            if max(max0, maxk) > 65535:
-                raise _lib.KpgnnError(f"edge code {max(max0, maxk)} exceeds the uint16 code range")
-            c = KHopCSR()
-            c.N, c.K, c.E, c.A, c.device = N, K, E, int(A), dev
-            c.max_code0, c.max_codek = int(max0), int(maxk)
-            S = N * K
-            i32 = dict(dtype=torch.int32, device=dev)
-            c.rowptr_dst = torch.empty(S + 1, **i32)
-            c.rowptr_src = torch.empty(S + 1, **i32)
-            c.col_dst = torch.empty(max(c.A, 1), **i32)
-            c.col_src = torch.empty(max(c.A, 1), **i32)
-            c.code_dst = torch.empty(max(c.A, 1), dtype=torch.int16, device=dev)  # uint16 payload
-            c.code_src = torch.empty(max(c.A, 1), dtype=torch.int16, device=dev)
-            c.nodes_per_tile = nodes_per_tile if nodes_per_tile is not None else KHopCSR.NODES_PER_TILE
-            ntiles = (N + c.nodes_per_tile - 1) // c.nodes_per_tile
-            c.tile_ptr = torch.empty(ntiles + 1, **i32) if nodes_per_tile is not None else None
-            c.tile_pack = torch.empty(max(c.A, 1), **i32) if nodes_per_tile is not None else None  # uint32 payload
-            ws_bytes = lib.kpgnn_csr_workspace_bytes(E, c.A, N, K)
-            ws = torch.empty(max(int(ws_bytes), 256), dtype=torch.uint8, device=dev)
-            _lib.check(lib.kpgnn_csr_build(edge_index.data_ptr(), ei_stride, edge_attr.data_ptr(), at_stride, E, K, N,
-                                           c.A, c.rowptr_dst.data_ptr(), c.col_dst.data_ptr(), c.code_dst.data_ptr(),
-                                           c.rowptr_src.data_ptr(), c.col_src.data_ptr(), c.code_src.data_ptr(),
-                                           c.nodes_per_tile, None if c.tile_ptr is None else c.tile_ptr.data_ptr(),
-                                           None if c.tile_pack is None else c.tile_pack.data_ptr(),
-                                           ws.data_ptr(), ctypes.c_size_t(ws.numel()), stream), "kpgnn_csr_build")
+        _lib.launch("kpgnn_csr_stats", dev, edge_index.data_ptr(), ei_stride, edge_attr.data_ptr(), at_stride, E, K, stats.data_ptr())
+        A, max0, maxk, minv, nmin, nmax = stats.tolist()[:6]  # the one host sync of a batch build
+        if minv < 0:
+            raise ValueError("edge_attr holds negative codes")
+        if E > 0 and (nmin < 0 or nmax >= N):
+            raise IndexError(f"edge_index out of range [0, {N}): min {nmin}, max {nmax}")
+        if max(max0, maxk) > 65535:
+            raise _lib.KpgnnError(f"edge code {max(max0, maxk)} exceeds the uint16 code range")
+        c = KHopCSR()
+        c.N, c.K, c.E, c.A, c.device = N, K, E, int(A), dev
+        c.max_code0, c.max_codek = int(max0), int(maxk)
+        S = N * K
+        i32 = dict(dtype=torch.int32, device=dev)
+        c.rowptr_dst = torch.empty(S + 1, **i32)
+        c.rowptr_src = torch.empty(S + 1, **i32)
+        c.col_dst = torch.empty(max(c.A, 1), **i32)
+        c.col_src = torch.empty(max(c.A, 1), **i32)
+        c.code_dst = torch.empty(max(c.A, 1), dtype=torch.int16, device=dev)  # uint16 payload
+        c.code_src = torch.empty(max(c.A, 1), dtype=torch.int16, device=dev)
+        c.nodes_per_tile = nodes_per_tile if nodes_per_tile is not None else KHopCSR.NODES_PER_TILE
+        ntiles = (N + c.nodes_per_tile - 1) // c.nodes_per_tile
+        c.tile_ptr = torch.empty(ntiles + 1, **i32) if nodes_per_tile is not None else None
+        c.tile_pack = torch.empty(max(c.A, 1), **i32) if nodes_per_tile is not None else None  # uint32 payload
+        ws_bytes = lib.kpgnn_csr_workspace_bytes(E, c.A, N, K)
+        ws = torch.empty(max(int(ws_bytes), 256), dtype=torch.uint8, device=dev)
+        _lib.launch("kpgnn_csr_build", dev, edge_index.data_ptr(), ei_stride, edge_attr.data_ptr(), at_stride, E, K, N,
+                    c.A, c.rowptr_dst.data_ptr(), c.col_dst.data_ptr(), c.code_dst.data_ptr(),
+                    c.rowptr_src.data_ptr(), c.col_src.data_ptr(), c.code_src.data_ptr(),
+                    c.nodes_per_tile, None if c.tile_ptr is None else c.tile_ptr.data_ptr(),
+                    None if c.tile_pack is None else c.tile_pack.data_ptr(), ws.data_ptr(), ctypes.c_size_t(ws.numel()))
         return c
 
 

@@ -5,43 +5,10 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import MODE_GCN, MODE_GIN, MODE_GINPLUS, MODE_SUM
+from ._lib import MODE_GCN, MODE_GIN, MODE_GINPLUS, MODE_SUM, LaunchTimer, set_launch_timer  # noqa: F401
 
 _SQRT1_2 = 0.7071067811865476
 _INV_SQRT_2PI = 0.3989422804014327
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-class LaunchTimer:
-    """Opt-in per-launch timing of the aggregation kernels with HIP events recorded on the stream the
-    kernel is launched on (bench.py's roofline leg).  Each record: (kind, algorithmic_bytes, start, stop)."""
-
-    def __init__(self):
-        self.records = []
-
-    def summary(self):
-        """kind -> dict(launches, avg_ms, bytes_per_launch, gbps); call after a device synchronize."""
-        out = {}
-        for kind, nbytes, a, b in self.records:
-            d = out.setdefault(kind, {"launches": 0, "ms": 0.0, "bytes": 0})
-            d["launches"] += 1
-            d["ms"] += a.elapsed_time(b)
-            d["bytes"] += nbytes
-        for d in out.values():
-            d["avg_ms"] = d["ms"] / d["launches"]
-            d["bytes_per_launch"] = d["bytes"] / d["launches"]
-            d["gbps"] = d["bytes"] / (d["ms"] * 1e-3) / 1e9 if d["ms"] > 0 else 0.0
-        return out
-
-
-_timer = None
-
-def set_launch_timer(timer):
-    global _timer
-    _timer = timer
 
 
 def algorithmic_bytes(csr, k_act, D, n_tensors, n_rows_tables, extra_nd=0, s=4):
@@ -174,9 +141,7 @@ class deferred_reductions:
 
 def flush_reductions(jobs):
     arr = (_lib.ReduceJob * len(jobs))(*[j for j, _ in jobs])
-    dev = jobs[0][1][0].device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().kpgnn_reduce_jobs(arr, len(jobs), torch.cuda.current_stream(dev).cuda_stream), "kpgnn_reduce_jobs")
+    _lib.launch("kpgnn_reduce_jobs", jobs[0][1][0].device, arr, len(jobs))
 
 
 _deferred_owners = set()      # data_ptr of the parameters whose gradient a queued job will write
@@ -249,7 +214,6 @@ def aggregate_fwd_raw(csr, k_act, mode, x, table0, tablek, periph, eps, theta, x
     """Launch kpgnn_aggregate_fwd.  x is [N,k,D], or None with xs = k per-hop [N,D] tensors (row stride shared).
     bf16: xs are bf16 rows and `pre` is returned as bf16 (KPGNN_STORE_BF16).
     Returns (out or hout, pre or None)."""
-    lib = _lib.load()
     if x is not None:
         N, K, D = x.shape
     else:
@@ -296,18 +260,13 @@ def aggregate_fwd_raw(csr, k_act, mode, x, table0, tablek, periph, eps, theta, x
     else:
         out = torch.empty((N, K, D), dtype=torch.float32, device=dev)
         d.out, d.o_sn, d.o_sk = out.data_ptr(), out.stride(0), out.stride(1)
-    with torch.cuda.device(dev):
-        if _timer is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(lib.kpgnn_aggregate_fwd(ctypes.byref(d), _stream(out)), "kpgnn_aggregate_fwd")
-        if _timer is not None:
-            e1.record()
-            n_t = 1 + (periph is not None) + (pre is not None) + (theta is None)  # x, dense P, pre, out
-            extra = 4 * N * K if uid is not None else 0                           # int32 uid per (node,hop)
-            _timer.records.append(("agg_fwd", extra + algorithmic_bytes(csr, K, D, n_t, d.n_code0 + d.n_codek,
-                                                                        extra_nd=1 if theta is not None else 0,
-                                                                        s=2 if bf16 else 4), e0, e1))
+
+    def nbytes():
+        n_t = 1 + (periph is not None) + (pre is not None) + (theta is None)  # x, dense P, pre, out
+        extra = 4 * N * K if uid is not None else 0                           # int32 uid per (node,hop)
+        return extra + algorithmic_bytes(csr, K, D, n_t, d.n_code0 + d.n_codek, extra_nd=1 if theta is not None else 0,
+                                         s=2 if bf16 else 4)
+    _lib.launch("kpgnn_aggregate_fwd", dev, ctypes.byref(d), timed=("agg_fwd", nbytes))
     return out, pre
 
 
@@ -326,7 +285,6 @@ def khop_pull_gather(csr, slabs, hinit, hinit2=None):
     and `hinit`): out[i] = hinit[i] + sum_k sum_{j in N_k(i)} slabs[k][j], where slabs[k] is hop k's [N,D] slab of dL/dS of the
     layer that read the state at hop slot k.  Replaces one read-modify-write of the state's gradient per reader (36 per step
     at K = L = 8: agg_bwd moved 273 MB per launch for 183 MB of gathered rows) by one write per state."""
-    lib = _lib.load()
     K = len(slabs)
     N, D = slabs[0].shape
     dev = slabs[0].device
@@ -345,15 +303,8 @@ def khop_pull_gather(csr, slabs, hinit, hinit2=None):
         assert t.shape == (N, D) and t.is_contiguous() and t.dtype == torch.float32
         d.x_slot[k] = t.data_ptr()
     d.theta, d.hout, d.hinit, d.hinit2 = ones.data_ptr(), out.data_ptr(), _ptr(hinit), _ptr(hinit2)
-    with torch.cuda.device(dev):
-        if _timer is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(lib.kpgnn_aggregate_fwd(ctypes.byref(d), _stream(out)), "kpgnn_aggregate_fwd (pull gather)")
-        if _timer is not None:
-            e1.record()
-            _timer.records.append(("agg_bwd", algorithmic_bytes(csr, K, D, 1, 0, extra_nd=1 + (hinit is not None) + (hinit2 is not None)),
-                                   e0, e1))
+    _lib.launch("kpgnn_aggregate_fwd", dev, ctypes.byref(d), timed=("agg_bwd", lambda: algorithmic_bytes(
+        csr, K, D, 1, 0, extra_nd=1 + (hinit is not None) + (hinit2 is not None))))
     return out
 
 
@@ -361,7 +312,6 @@ def aggregate_bwd_raw(csr, k_act, mode, g, eps, n_code0, n_codek, want_tables, s
     """Launch kpgnn_aggregate_bwd on g = dL/dS.  Returns (gx, gtable0, gtablek); with slots=True gx is a list of
     k contiguous [N,D] tensors (one per hop slot) instead of one [N,k,D] tensor; slot_bufs[k] (a [N,D] tensor or None)
     makes the kernel ADD slot k's gradient into that buffer instead of writing a fresh one."""
-    lib = _lib.load()
     N, K, D = g.shape
     dev = g.device
     bf16 = g.dtype == torch.bfloat16      # KPGNN_STORE_BF16: g rows are bf16, gx stays fp32
@@ -414,16 +364,9 @@ def aggregate_bwd_raw(csr, k_act, mode, g, eps, n_code0, n_codek, want_tables, s
         if K > 1 and n_codek > 0:
             gtk = torch.zeros((n_codek, D), dtype=torch.float32, device=dev)
             d.gtablek = gtk.data_ptr()
-    with torch.cuda.device(dev):
-        if _timer is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(lib.kpgnn_aggregate_bwd(ctypes.byref(d), _stream(g)), "kpgnn_aggregate_bwd")
-        if _timer is not None:
-            e1.record()
-            # g read (2 or 4 bytes per element) + gx written (fp32)
-            _timer.records.append(("agg_bwd", algorithmic_bytes(csr, K, D, 1.5 if bf16 else 2,
-                                                                (n_code0 + n_codek) if want_tables else 0), e0, e1))
+    # g read (2 or 4 bytes per element) + gx written (fp32)
+    _lib.launch("kpgnn_aggregate_bwd", dev, ctypes.byref(d), timed=("agg_bwd", lambda: algorithmic_bytes(
+        csr, K, D, 1.5 if bf16 else 2, (n_code0 + n_codek) if want_tables else 0)))
     for k, b in late_adds:
         gx[k] = b.add_(gx[k])
     return gx, gt0, gtk
@@ -445,9 +388,7 @@ def dict_tile_pack(csr, uid):
         N = uid.shape[0]
         tiles = (N + csr.nodes_per_tile - 1) // csr.nodes_per_tile
         pack = hit[0] if hit is not None else torch.empty((tiles, 64), dtype=torch.int32, device=uid.device)
-        with torch.cuda.device(uid.device):
-            _lib.check(_lib.load().kpgnn_dict_tile_pack(uid.data_ptr(), kf, N, kf, csr.nodes_per_tile, pack.data_ptr(),
-                                                        _stream(uid)), "kpgnn_dict_tile_pack")
+        _lib.launch("kpgnn_dict_tile_pack", uid.device, uid.data_ptr(), kf, N, kf, csr.nodes_per_tile, pack.data_ptr())
         hit = cache[key] = (pack, kf, uid)     # (uid kept alive: the key is its address)
     return hit[0], hit[1]
 
@@ -480,14 +421,7 @@ def dict_grad_raw(uid, n_dict, theta, gh, defer=False):
     ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
     d.gdict, d.workspace, d.workspace_bytes = gd.data_ptr(), ws.data_ptr(), int(ws_bytes)
     d.defer_reduce = 1 if defer else 0
-    with torch.cuda.device(dev):
-        if _timer is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(lib.kpgnn_dict_grad(ctypes.byref(d), _stream(gh)), "kpgnn_dict_grad")
-        if _timer is not None:
-            e1.record()
-            _timer.records.append(("dict_grad", 4 * N * D + 4 * N * K + 4 * D * (n_dict + K), e0, e1))
+    _lib.launch("kpgnn_dict_grad", dev, ctypes.byref(d), timed=("dict_grad", lambda: 4 * N * D + 4 * N * K + 4 * D * (n_dict + K)))
     if defer:
         return gd, ws, int(lib.kpgnn_dict_grad_slabs(N))
     return gd
@@ -541,14 +475,8 @@ def dict_grad_multi_raw(items, n_dict):
     gd = torch.empty((n_dict, D), dtype=torch.float32, device=dev)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     d.gdict, d.workspace, d.workspace_bytes = gd.data_ptr(), ws.data_ptr(), ws_bytes
-    with torch.cuda.device(dev):
-        if _timer is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(lib.kpgnn_dict_grad_multi(ctypes.byref(d), _stream(gd)), "kpgnn_dict_grad_multi")
-        if _timer is not None:
-            e1.record()
-            _timer.records.append(("dict_grad", len(items) * 4 * N * D + 4 * N * K + 4 * D * n_dict, e0, e1))
+    _lib.launch("kpgnn_dict_grad_multi", dev, ctypes.byref(d),
+                timed=("dict_grad", lambda: len(items) * 4 * N * D + 4 * N * K + 4 * D * n_dict))
     return gd
 
 
@@ -598,15 +526,9 @@ def table_grad_raw(csr, g, n_code0, n_codek, edges=True, uid=None, n_dict=0, the
     d.workspace, d.workspace_bytes = ws.data_ptr(), int(ws_bytes)
     if extra is not None:       # (out, slab, nslab) of dict_grad_raw(defer=True): added up by this call's finishing launch
         d.extra_out, d.extra_slab, d.extra_nslab, d.extra_elems = extra[0].data_ptr(), extra[1].data_ptr(), extra[2], extra[0].numel()
-    with torch.cuda.device(dev):
-        if _timer is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(lib.kpgnn_table_grad(ctypes.byref(d), _stream(g)), "kpgnn_table_grad")
-        if _timer is not None:
-            e1.record()
-            _timer.records.append(("table_grad", g.element_size() * N * K * D + (4 * csr.active_pairs(K) if edges else 0)
-                                   + 4 * D * (n0 + nk + n_dict) + (4 * N * K if n_dict else 0), e0, e1))
+    _lib.launch("kpgnn_table_grad", dev, ctypes.byref(d), timed=("table_grad", lambda: (
+        g.element_size() * N * K * D + (4 * csr.active_pairs(K) if edges else 0) + 4 * D * (n0 + nk + n_dict)
+        + (4 * N * K if n_dict else 0))))
     return gt0, gtk, gd
 
 
@@ -695,15 +617,9 @@ def combine_table_grad_raw(csr, pre, gh, theta, ptab, uid, n_code0, n_codek, wan
     waiting = take_reduce_job()        # (an earlier launch's deferred reduction rides along with the finishing launch)
     if waiting is not None:
         d.pending = ctypes.cast(ctypes.pointer(waiting[0]), ctypes.c_void_p)
-    with torch.cuda.device(dev):
-        if _timer is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(lib.kpgnn_table_grad(ctypes.byref(d), _stream(pre)), "kpgnn_table_grad")
-        if _timer is not None:
-            e1.record()     # S read, g written, gh read, pair list, tables
-            _timer.records.append(("combine_table_grad", 8 * N * K * D + 4 * N * D + 4 * csr.active_pairs(K)
-                                   + 4 * D * (n_code0 + nk), e0, e1))
+    # bytes: S read, g written, gh read, pair list, tables
+    _lib.launch("kpgnn_table_grad", dev, ctypes.byref(d), timed=("combine_table_grad", lambda: (
+        8 * N * K * D + 4 * N * D + 4 * csr.active_pairs(K) + 4 * D * (n_code0 + nk))))
     if dict_rows > 0:
         return g, ((gth, gal) if gal is not None else gth), gt0, gtk, gd
     return g, ((gth, gal) if gal is not None else gth), gt0, gtk
@@ -742,15 +658,9 @@ def combine_bwd_raw(mode, pre, gout, theta, periph, ptab, uid, want_gtheta, want
         nb = lib.kpgnn_combine_bwd_workspace_bytes(N, K, D)
         ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
         d.workspace, d.workspace_bytes = ws.data_ptr(), int(nb)
-    with torch.cuda.device(dev):
-        if _timer is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(lib.kpgnn_combine_bwd(ctypes.byref(d), _stream(pre)), "kpgnn_combine_bwd")
-        if _timer is not None:
-            e1.record()
-            n_t = 2 + (gv is not None) + (theta is None) + (periph is not None and want_gtheta)
-            _timer.records.append(("combine_bwd", (2 if bf16 else 4) * N * K * D * n_t + (4 * N * D if theta is not None else 0), e0, e1))
+    _lib.launch("kpgnn_combine_bwd", dev, ctypes.byref(d), timed=("combine_bwd", lambda: (
+        (2 if bf16 else 4) * N * K * D * (2 + (gv is not None) + (theta is None) + (periph is not None and want_gtheta))
+        + (4 * N * D if theta is not None else 0))))
     if gal is not None:
         return g, gv, (gth, gal)
     return g, gv, gth
@@ -1049,10 +959,8 @@ def _finish_gtheta(ctx, gtheta, theta, galphas_done, k_act):
     """d/dalphas through theta (geo_theta.hip) when the finishing launch has not already produced it."""
     if gtheta is not None and ctx.alphas is not None and not galphas_done:
         galpha = torch.empty_like(ctx.alphas)
-        lib = _lib.load()
-        with torch.cuda.device(galpha.device):
-            _lib.check(lib.kpgnn_geo_theta_bwd(ctx.alphas.data_ptr(), theta.data_ptr(), gtheta.data_ptr(), k_act,
-                                               ctx.alphas.numel(), galpha.data_ptr(), _stream(galpha)), "kpgnn_geo_theta_bwd")
+        _lib.launch("kpgnn_geo_theta_bwd", galpha.device,
+                    ctx.alphas.data_ptr(), theta.data_ptr(), gtheta.data_ptr(), k_act, ctx.alphas.numel(), galpha.data_ptr())
         return galpha
     return gtheta
 
@@ -1223,7 +1131,6 @@ class TableGatherSum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table, bias, idx, col_offset):
         _require_cuda(table, bias, idx, col_offset)
-        lib = _lib.load()
         table = table.contiguous()
         bias = bias.contiguous() if bias is not None else None
         M, C = idx.shape
@@ -1234,8 +1141,7 @@ class TableGatherSum(torch.autograd.Function):
         d.n_dyn = dyn_ptr(M)
         d.idx, d.col_offset, d.table, d.bias = idx.data_ptr(), col_offset.data_ptr(), table.data_ptr(), _ptr(bias)
         d.out, d.out_stride = out.data_ptr(), out.stride(0)
-        with torch.cuda.device(table.device):
-            _lib.check(lib.kpgnn_table_gather_sum_fwd(ctypes.byref(d), _stream(table)), "kpgnn_table_gather_sum_fwd")
+        _lib.launch("kpgnn_table_gather_sum_fwd", table.device, ctypes.byref(d))
         ctx.save_for_backward(idx, col_offset)
         ctx.shape = (R, D)
         ctx.has_bias = bias is not None
@@ -1257,8 +1163,7 @@ class TableGatherSum(torch.autograd.Function):
         d.idx, d.col_offset = idx.data_ptr(), col_offset.data_ptr()
         d.gout, d.gout_stride, d.gtable = gout.data_ptr(), gout.stride(0), gtable.data_ptr()
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-        with torch.cuda.device(gout.device):
-            _lib.check(lib.kpgnn_table_gather_sum_bwd(ctypes.byref(d), _stream(gout)), "kpgnn_table_gather_sum_bwd")
+        _lib.launch("kpgnn_table_gather_sum_bwd", gout.device, ctypes.byref(d))
         if ctx.has_bias:
             refuse_dynamic_rows("the bias gradient of a table gather-sum (framework row sum)", M)
         gbias = gout.sum(0) if ctx.has_bias else None
@@ -1376,7 +1281,6 @@ class SegmentPool(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, batch, ptr, num_graphs, mean):
-        lib = _lib.load()
         x = _last_contig(x)
         N, D = x.shape
         out = torch.empty((num_graphs, D), dtype=torch.float32, device=x.device)
@@ -1384,8 +1288,7 @@ class SegmentPool(torch.autograd.Function):
         d.N, d.G, d.D, d.mode = N, num_graphs, D, 1 if mean else 0
         d.n_dyn = dyn_ptr(N)
         d.graph_ptr, d.x, d.x_stride, d.out = ptr.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr()
-        with torch.cuda.device(x.device):
-            _lib.check(lib.kpgnn_segment_pool_fwd(ctypes.byref(d), _stream(x)), "kpgnn_segment_pool_fwd")
+        _lib.launch("kpgnn_segment_pool_fwd", x.device, ctypes.byref(d))
         ctx.save_for_backward(batch, ptr)
         ctx.dims = (N, D, num_graphs, mean)
         return out
@@ -1394,15 +1297,13 @@ class SegmentPool(torch.autograd.Function):
     def backward(ctx, gout):
         batch, ptr = ctx.saved_tensors
         N, D, G, mean = ctx.dims
-        lib = _lib.load()
         gout = gout.contiguous()
         gx = torch.empty((N, D), dtype=torch.float32, device=gout.device)
         d = _lib.PoolDesc()
         d.N, d.G, d.D, d.mode = N, G, D, 1 if mean else 0
         d.n_dyn = dyn_ptr(N)
         d.graph_ptr, d.batch, d.gout, d.gx, d.gx_stride = ptr.data_ptr(), batch.data_ptr(), gout.data_ptr(), gx.data_ptr(), D
-        with torch.cuda.device(gout.device):
-            _lib.check(lib.kpgnn_segment_pool_bwd(ctypes.byref(d), _stream(gout)), "kpgnn_segment_pool_bwd")
+        _lib.launch("kpgnn_segment_pool_bwd", gout.device, ctypes.byref(d))
         return gx, None, None, None, None
 
 
@@ -1428,7 +1329,6 @@ class EncTables(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, squash, mults, ncomps, *tensors):
-        lib = _lib.load()
         ne = len(ncomps)
         enc_t, embs = tensors[:3 * ne], tensors[3 * ne:]
         _require_cuda(*tensors)
@@ -1441,8 +1341,7 @@ class EncTables(torch.autograd.Function):
         bias = torch.empty((H,), dtype=torch.float32, device=dev)
         d = EncTables._desc(squash, mults, ncomps, enc_t, embs, H)
         d.table, d.pre, d.bias = out[0].data_ptr(), out[1].data_ptr(), bias.data_ptr()
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_enc_tables_fwd(ctypes.byref(d), _stream(bias)), "kpgnn_enc_tables_fwd")
+        _lib.launch("kpgnn_enc_tables_fwd", dev, ctypes.byref(d))
         ctx.save_for_backward(out, *enc_t, *embs)
         ctx.meta = (squash, tuple(mults), tuple(ncomps), H)
         return out[0], bias
@@ -1470,7 +1369,6 @@ class EncTables(torch.autograd.Function):
         squash, mults, ncomps, H = ctx.meta
         ne = len(ncomps)
         enc_t, embs = rest[:3 * ne], rest[3 * ne:]
-        lib = _lib.load()
         dev = out.device
         gtable = gtable.contiguous() if gtable is not None else torch.zeros_like(out[0])
         gbias = gbias.contiguous() if gbias is not None else torch.zeros(H, dtype=torch.float32, device=dev)
@@ -1484,8 +1382,7 @@ class EncTables(torch.autograd.Function):
         g_emb = [torch.empty_like(e) for e in embs]
         for c, g in enumerate(g_emb):
             d.comp_gemb[c] = g.data_ptr()
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_enc_tables_bwd(ctypes.byref(d), _stream(gtable)), "kpgnn_enc_tables_bwd")
+        _lib.launch("kpgnn_enc_tables_bwd", dev, ctypes.byref(d))
         return (None, None, None, *g_enc, *g_emb)
 
 

@@ -10,7 +10,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import _last_contig, _ptr, _stream, refuse_dynamic_rows
+from .ops import _last_contig, _ptr, refuse_dynamic_rows
 
 
 def _wgrad(dy, x, want_bias):
@@ -27,15 +27,13 @@ def _wgrad(dy, x, want_bias):
     d.N, d.O, d.I = N, O, I
     d.dy, d.dy_stride, d.x, d.x_stride = dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0)
     d.dw, d.db, d.workspace, d.workspace_bytes = dw.data_ptr(), _ptr(db), ws.data_ptr(), int(nb)
-    with torch.cuda.device(dev):
-        _lib.check(lib.kpgnn_linear_wgrad(ctypes.byref(d), _stream(dy)), "kpgnn_linear_wgrad")
+    _lib.launch("kpgnn_linear_wgrad", dev, ctypes.byref(d))
     return dw, db
 
 
 class AttentionCombineFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r):
-        lib = _lib.load()
         x = _last_contig(x.float())
         N, K, D = x.shape
         refuse_dynamic_rows("the attention combine (its products run over every row)", N)
@@ -54,15 +52,13 @@ class AttentionCombineFn(torch.autograd.Function):
         d.x, d.x_sn, d.x_sk = x.data_ptr(), x.stride(0), x.stride(1)
         d.gin, d.whh, d.acts, d.hsum, d.w, d.out = (gin.data_ptr(), whh.data_ptr(), acts.data_ptr(), hsum.data_ptr(),
                                                     w.data_ptr(), out.data_ptr())
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_attn_fwd(ctypes.byref(d), _stream(x)), "kpgnn_attn_fwd")
+        _lib.launch("kpgnn_attn_fwd", dev, ctypes.byref(d))
         ctx.save_for_backward(x, w_cat, whh, acts, w)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         x, w_cat, whh, acts, w = ctx.saved_tensors
-        lib = _lib.load()
         gout = gout.contiguous()
         N, K, D = x.shape
         dev = x.device
@@ -77,8 +73,7 @@ class AttentionCombineFn(torch.autograd.Function):
         d.x, d.x_sn, d.x_sk = x.data_ptr(), x.stride(0), x.stride(1)
         d.gin, d.whh, d.acts, d.hsum, d.w = gin_dummy.data_ptr(), whh.data_ptr(), acts.data_ptr(), hsum.data_ptr(), w.data_ptr()
         d.gout, d.dx, d.ds, d.dgin, d.hprev = gout.data_ptr(), dx.data_ptr(), ds.data_ptr(), dgin.data_ptr(), hprev.data_ptr()
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_attn_bwd(ctypes.byref(d), _stream(x)), "kpgnn_attn_bwd")
+        _lib.launch("kpgnn_attn_bwd", dev, ctypes.byref(d))
         # dx += dgin @ W_ih   (library GEMM, accumulated into the direct part written by the kernel)
         dxf = dx.view(N * K, D)
         dxf.addmm_(dgin, w_cat)
@@ -116,7 +111,6 @@ class AttentionScanFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, *params):
-        lib = _lib.load()
         N, K, D = x.shape
         refuse_dynamic_rows("the attention combine (its products run over every row)", N)
         dev = x.device
@@ -128,15 +122,13 @@ class AttentionScanFn(torch.autograd.Function):
         w_pad = torch.empty((64, D), dtype=torch.float32, device=dev)
         d = _scan_desc(x, params, acts, hsum, w)
         d.out, d.w_pad = out.data_ptr(), w_pad.data_ptr()
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_attn_scan_fwd(ctypes.byref(d), _stream(x)), "kpgnn_attn_scan_fwd")
+        _lib.launch("kpgnn_attn_scan_fwd", dev, ctypes.byref(d))
         ctx.save_for_backward(x, acts, w, w_pad, *params)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         x, acts, w, w_pad, *params = ctx.saved_tensors
-        lib = _lib.load()
         gout = gout.contiguous()
         N, K, D = x.shape
         dev = x.device
@@ -150,16 +142,15 @@ class AttentionScanFn(torch.autograd.Function):
         d.w_pad = w_pad.data_ptr()
         d.gout, d.dx, d.ds, d.dgin = gout.data_ptr(), dx.data_ptr(), ds.data_ptr(), dgin.data_ptr()
         d.whh_slab, d.dwhh_pad = slab.data_ptr(), dwhh_pad.data_ptr()
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_attn_scan_bwd(ctypes.byref(d), _stream(x)), "kpgnn_attn_scan_bwd")   # ds, dgin, dwhh_pad, dx
+        _lib.launch("kpgnn_attn_scan_bwd", dev, ctypes.byref(d))   # ds, dgin, dwhh_pad, dx
         xf = x.reshape(N * K, D)
         dw_pad, db_pad = _wgrad(dgin, xf, True)                          # [64, D], [64]
         dw = torch.empty((2, 4 * K, D), dtype=torch.float32, device=dev)
         db = torch.empty((2, 4 * K), dtype=torch.float32, device=dev)
         dwhh = torch.empty((2, 4 * K, K), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_attn_scan_unpad(dw_pad.data_ptr(), db_pad.data_ptr(), dwhh_pad.data_ptr(), dw.data_ptr(),
-                                                 db.data_ptr(), dwhh.data_ptr(), K, D, _stream(x)), "kpgnn_attn_scan_unpad")
+        _lib.launch("kpgnn_attn_scan_unpad", dev,
+                    dw_pad.data_ptr(), db_pad.data_ptr(), dwhh_pad.data_ptr(), dw.data_ptr(), db.data_ptr(), dwhh.data_ptr(),
+                    K, D)
         return dx, dw[0], dwhh[0], db[0], db[0], dw[1], dwhh[1], db[1], db[1]
 
 

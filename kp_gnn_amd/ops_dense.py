@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .ops import _ptr, _stream, dyn_ptr, refuse_dynamic_rows
+from .ops import _ptr, dyn_ptr, refuse_dynamic_rows
 
 
 # ------------------------------------------------------------------------------------------- column-statistics slots
@@ -82,7 +82,6 @@ def _column_stats_of(t):
 class BatchNormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, running_mean, running_var, eps, momentum, relu, nbt=None, ready_slot=None):
-        lib = _lib.load()
         x = x if x.stride(-1) == 1 else x.contiguous()
         N, C = x.shape
         dev = x.device
@@ -102,8 +101,7 @@ class BatchNormAct(torch.autograd.Function):
             d.residual, d.r_stride = residual.data_ptr(), residual.stride(0)
         d.stat_slot, d.stats_ready = slot.data_ptr(), 1 if ready_slot is not None else 0
         d.num_batches_tracked = _ptr(nbt)
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_bn_fwd(ctypes.byref(d), _stream(x)), "kpgnn_bn_fwd")
+        _lib.launch("kpgnn_bn_fwd", dev, ctypes.byref(d))
         ctx.save_for_backward(x, gamma, beta, stats)
         ctx.relu = relu
         ctx.has_res = residual is not None
@@ -113,7 +111,6 @@ class BatchNormAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dz):
         x, gamma, beta, stats = ctx.saved_tensors
-        lib = _lib.load()
         dz = dz if dz.stride(-1) == 1 else dz.contiguous()
         N, C = x.shape
         dev = x.device
@@ -133,8 +130,7 @@ class BatchNormAct(torch.autograd.Function):
         d.stat_slot = slot.data_ptr()
         if rbuf is not None:
             d.residual_grad, d.rg_stride = rbuf.data_ptr(), rbuf.stride(0)
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_bn_bwd(ctypes.byref(d), _stream(x)), "kpgnn_bn_bwd")
+        _lib.launch("kpgnn_bn_bwd", dev, ctypes.byref(d))
         gres = None if (not ctx.has_res or rbuf is not None) else dz
         return dx, dgb[0], dgb[1], gres, None, None, None, None, None, None, None
 
@@ -170,7 +166,7 @@ def _mfma_linear(x, w, bias, transposed=False):
     d.w_transposed = 1 if transposed else 0
     d.x, d.x_stride, d.w, d.bias, d.y, d.y_stride = x.data_ptr(), x.stride(0), w.data_ptr(), _ptr(bias), y.data_ptr(), y.stride(0)
     with torch.cuda.device(x.device):
-        rc = lib.kpgnn_linear_fwd(ctypes.byref(d), _stream(x))
+        rc = lib.kpgnn_linear_fwd(ctypes.byref(d), torch.cuda.current_stream(x.device).cuda_stream)
     if rc == -3:
         return None
     _lib.check(rc, "kpgnn_linear_fwd")
@@ -215,8 +211,7 @@ class LinearWgrad(torch.autograd.Function):
         d.n_dyn = dyn_ptr(N)
         d.dy, d.dy_stride, d.x, d.x_stride = dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0)
         d.dw, d.db, d.workspace, d.workspace_bytes = dw.data_ptr(), _ptr(db), ws.data_ptr(), int(nb)
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_linear_wgrad(ctypes.byref(d), _stream(dy)), "kpgnn_linear_wgrad")
+        _lib.launch("kpgnn_linear_wgrad", dev, ctypes.byref(d))
         return dx, dw, db
 
 
@@ -288,11 +283,9 @@ def prepare_mlp_splits(mlps, num_rows):
         jobs[j].w, jobs[j].wn, jobs[j].wk, jobs[j].O, jobs[j].I, jobs[j].frag = w.data_ptr(), wn, wk, O, I, frag.data_ptr()
         _split_cache[(w.data_ptr(), tr)] = (w._version, O, I, frag)
         off += nb
-    with torch.cuda.device(dev):
-        for a in range(0, len(todo), 64):
-            n = min(64, len(todo) - a)
-            chunk = (_lib.SplitJob * n)(*jobs[a:a + n])
-            _lib.check(lib.kpgnn_linear_split_many(chunk, n, torch.cuda.current_stream(dev).cuda_stream), "kpgnn_linear_split_many")
+    for a in range(0, len(todo), 64):
+        n = min(64, len(todo) - a)
+        _lib.launch("kpgnn_linear_split_many", dev, (_lib.SplitJob * n)(*jobs[a:a + n]), n)
 
 
 def _lin_bn(lib, dev, **kw):
@@ -308,8 +301,7 @@ def _lin_bn(lib, dev, **kw):
         ws = _split_workspace(lib, kw["O"], kw["I"], 1, dev)          # (the bf16-split kernel's copy of W; None: fp32 kernel)
         if ws is not None:
             d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    with torch.cuda.device(dev):
-        _lib.check(lib.kpgnn_linear_bn(ctypes.byref(d), torch.cuda.current_stream(dev).cuda_stream), "kpgnn_linear_bn")
+    _lib.launch("kpgnn_linear_bn", dev, ctypes.byref(d))
 
 
 class FusedMLP(torch.autograd.Function):
@@ -372,8 +364,7 @@ class FusedMLP(torch.autograd.Function):
                 d.residual, d.r_stride = residual.data_ptr(), residual.stride(0)
                 ctx.has_res = True
                 ctx.res_cell = getattr(residual, "_kp_slot_cell", None)
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_bn_fwd(ctypes.byref(d), _stream(h)), "kpgnn_bn_fwd")
+        _lib.launch("kpgnn_bn_fwd", dev, ctypes.byref(d))
         if outer:
             ctx.save_for_backward(h, w0c, w3c, g1, be1, g2, be2, y1, y2, st, gO)
         else:
@@ -419,8 +410,7 @@ class FusedMLP(torch.autograd.Function):
             d.outer_mean, d.outer_invstd = st[4].data_ptr(), st[5].data_ptr()
             if rbuf is not None:
                 d.residual_grad, d.rg_stride = rbuf.data_ptr(), rbuf.stride(0)
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_bn_bwd(ctypes.byref(d), _stream(h)), "kpgnn_bn_bwd")
+        _lib.launch("kpgnn_bn_bwd", dev, ctypes.byref(d))
         okw = dict(pro=3, o_mean=st[4], o_invstd=st[5], o_gamma=gO, o_dgamma=gb[4], o_dbeta=gb[5]) if ctx.outer else dict(pro=2)
         _lin_bn(lib, dev, N=N, O=O, I=O, x=dz, w=w3, y=da1, w_transposed=1, epi=2, pro_relu=1, in_slot=slot2,
                 in_gamma=g2, in_beta=be2, in_mean=st[2], in_invstd=st[3], x2=y2, xt=dy2, dgamma=gb[0], dbeta=gb[1],
@@ -440,24 +430,23 @@ class FusedMLP(torch.autograd.Function):
         b.N, b.O, b.I = N, O, I
         b.dy, b.dy_stride, b.x, b.x_stride = dy1.data_ptr(), O, h.data_ptr(), I
         b.dw, b.db = dw0.data_ptr(), db[1].data_ptr()
-        with torch.cuda.device(dev):
-            if I == O:
-                from . import ops
-                nb = 2 * int(lib.kpgnn_wgrad_workspace_bytes(O, O))
+        if I == O:
+            from . import ops
+            nb = 2 * int(lib.kpgnn_wgrad_workspace_bytes(O, O))
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), nb
+            job = ops.defer_reduce_job(w0, w3)    # (inside ops.deferred_reductions(): the reduce rides with a later launch)
+            if job is not None:
+                a.defer = ctypes.cast(ctypes.pointer(job), ctypes.c_void_p)
+            _lib.launch("kpgnn_linear_wgrad_pair", dev, ctypes.byref(a), ctypes.byref(b))
+            if job is not None:
+                ops.queue_reduce_job(job, (ws, dw3, dw0, db))
+        else:
+            for q in (a, b):
+                nb = int(lib.kpgnn_wgrad_workspace_bytes(q.O, q.I))
                 ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-                a.workspace, a.workspace_bytes = ws.data_ptr(), nb
-                job = ops.defer_reduce_job(w0, w3)    # (inside ops.deferred_reductions(): the reduce rides with a later launch)
-                if job is not None:
-                    a.defer = ctypes.cast(ctypes.pointer(job), ctypes.c_void_p)
-                _lib.check(lib.kpgnn_linear_wgrad_pair(ctypes.byref(a), ctypes.byref(b), _stream(h)), "kpgnn_linear_wgrad_pair")
-                if job is not None:
-                    ops.queue_reduce_job(job, (ws, dw3, dw0, db))
-            else:
-                for q in (a, b):
-                    nb = int(lib.kpgnn_wgrad_workspace_bytes(q.O, q.I))
-                    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-                    q.workspace, q.workspace_bytes = ws.data_ptr(), nb
-                    _lib.check(lib.kpgnn_linear_wgrad(ctypes.byref(q), _stream(h)), "kpgnn_linear_wgrad")
+                q.workspace, q.workspace_bytes = ws.data_ptr(), nb
+                _lib.launch("kpgnn_linear_wgrad", dev, ctypes.byref(q))
         gres = dz if (ctx.outer and ctx.has_res and rbuf is None and not handed) else None
         return (dh if ctx.needs_input_grad[0] else None, dw0, db[1] if ctx.has_b0 else None, gb[2], gb[3],
                 dw3, db[0] if ctx.has_b3 else None, gb[0], gb[1], None, None, None,
@@ -549,8 +538,7 @@ class JKConcatLinear(torch.autograd.Function):
             ws = _split_workspace(lib, O, H, len(states), weight.device)     # (the bf16-split kernel's copy of W; None: fp32 kernel)
             if ws is not None:
                 d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-            with torch.cuda.device(weight.device):
-                _lib.check(lib.kpgnn_linear_group_fwd(ctypes.byref(d), _stream(y)), "kpgnn_linear_group_fwd")
+            _lib.launch("kpgnn_linear_group_fwd", weight.device, ctypes.byref(d))
             ctx.save_for_backward(weight, y, *states)
             return y
         refuse_dynamic_rows("the jumping-knowledge projection outside the grouped-K kernels' shapes", states[0].shape[0])
@@ -574,37 +562,36 @@ class JKConcatLinear(torch.autograd.Function):
             N, O = y.shape
             dev = dy.device
             dw = db = None
-            with torch.cuda.device(dev):
-                G = torch.empty((S, N, H), dtype=torch.float32, device=dev)
-                d = _lib.LinearDesc()
-                d.N, d.O, d.I = N, S * H, O
-                d.n_dyn = dyn_ptr(N)
-                d.x, d.x_stride, d.w, d.y, d.y_stride = dy.data_ptr(), O, weight.data_ptr(), G.data_ptr(), H
-                d.w_transposed, d.y_block_cols, d.y_block_stride = 1, H, N * H
-                d.x_mask = y.data_ptr()                       # dL/d(pre-activation) = dy where the saved output is > 0
-                wsx = _split_workspace(lib, H, O, S, dev)
-                if wsx is not None:
-                    d.workspace, d.workspace_bytes = wsx.data_ptr(), wsx.numel()
-                _lib.check(lib.kpgnn_linear_fwd(ctypes.byref(d), _stream(dy)), "kpgnn_linear_fwd")
-                if ctx.needs_input_grad[0] or (ctx.has_bias and ctx.needs_input_grad[1]):
-                    from . import ops
-                    dw = torch.empty((O, S * H), dtype=torch.float32, device=dev)
-                    db = torch.empty((O,), dtype=torch.float32, device=dev)
-                    nb = int(lib.kpgnn_wgrad_group_workspace_bytes(O, H, S))
-                    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-                    q = _lib.WgradDesc()
-                    q.N, q.O, q.I = N, O, H
-                    q.n_dyn = dyn_ptr(N)
-                    q.dy, q.dy_stride, q.x, q.x_stride = dy.data_ptr(), O, states[0].data_ptr(), H
-                    q.dy_mask = y.data_ptr()
-                    q.dw, q.db, q.workspace, q.workspace_bytes = dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nb
-                    xs = (ctypes.c_void_p * S)(*[st.data_ptr() for st in states])
-                    job = ops.defer_reduce_job(weight)     # (inside ops.deferred_reductions(): the reduce rides with a later launch)
-                    if job is not None:
-                        q.defer = ctypes.cast(ctypes.pointer(job), ctypes.c_void_p)
-                    _lib.check(lib.kpgnn_linear_wgrad_group(ctypes.byref(q), xs, S, _stream(dy)), "kpgnn_linear_wgrad_group")
-                    if job is not None:
-                        ops.queue_reduce_job(job, (ws, dw, db))
+            G = torch.empty((S, N, H), dtype=torch.float32, device=dev)
+            d = _lib.LinearDesc()
+            d.N, d.O, d.I = N, S * H, O
+            d.n_dyn = dyn_ptr(N)
+            d.x, d.x_stride, d.w, d.y, d.y_stride = dy.data_ptr(), O, weight.data_ptr(), G.data_ptr(), H
+            d.w_transposed, d.y_block_cols, d.y_block_stride = 1, H, N * H
+            d.x_mask = y.data_ptr()                       # dL/d(pre-activation) = dy where the saved output is > 0
+            wsx = _split_workspace(lib, H, O, S, dev)
+            if wsx is not None:
+                d.workspace, d.workspace_bytes = wsx.data_ptr(), wsx.numel()
+            _lib.launch("kpgnn_linear_fwd", dev, ctypes.byref(d))
+            if ctx.needs_input_grad[0] or (ctx.has_bias and ctx.needs_input_grad[1]):
+                from . import ops
+                dw = torch.empty((O, S * H), dtype=torch.float32, device=dev)
+                db = torch.empty((O,), dtype=torch.float32, device=dev)
+                nb = int(lib.kpgnn_wgrad_group_workspace_bytes(O, H, S))
+                ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+                q = _lib.WgradDesc()
+                q.N, q.O, q.I = N, O, H
+                q.n_dyn = dyn_ptr(N)
+                q.dy, q.dy_stride, q.x, q.x_stride = dy.data_ptr(), O, states[0].data_ptr(), H
+                q.dy_mask = y.data_ptr()
+                q.dw, q.db, q.workspace, q.workspace_bytes = dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nb
+                xs = (ctypes.c_void_p * S)(*[st.data_ptr() for st in states])
+                job = ops.defer_reduce_job(weight)     # (inside ops.deferred_reductions(): the reduce rides with a later launch)
+                if job is not None:
+                    q.defer = ctypes.cast(ctypes.pointer(job), ctypes.c_void_p)
+                _lib.launch("kpgnn_linear_wgrad_group", dev, ctypes.byref(q), xs, S)
+                if job is not None:
+                    ops.queue_reduce_job(job, (ws, dw, db))
             parts = [G[l] for l in range(S)]
             if not ctx.has_bias:
                 db = None
@@ -642,7 +629,6 @@ class HopMlp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, s, w1, b1, w2, b2, theta, wc, bc):
-        lib = _lib.load()
         s = s.contiguous()
         N, K, DI = s.shape
         refuse_dynamic_rows("kpgnn_hop_mlp", N)
@@ -660,8 +646,7 @@ class HopMlp(torch.autograd.Function):
         d.s, d.w1, d.b1, d.w2, d.b2, d.theta = s.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), _ptr(theta)
         d.wc, d.bc = _ptr(wc), _ptr(bc)
         d.h1, d.h2, d.out = h[0].data_ptr(), h[1].data_ptr(), _ptr(out)
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_hop_mlp_fwd(ctypes.byref(d), _stream(s)), "kpgnn_hop_mlp_fwd")
+        _lib.launch("kpgnn_hop_mlp_fwd", dev, ctypes.byref(d))
         ctx.save_for_backward(s, w1, b1, w2, b2, theta, wc, bc, h)
         return out if theta is not None else h[1]
 
@@ -686,8 +671,7 @@ class HopMlp(torch.autograd.Function):
         d.h1, d.h2 = h[0].data_ptr(), h[1].data_ptr()
         d.gout, d.gs, d.gflat = gout.data_ptr(), gs.data_ptr(), gflat.data_ptr()
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws_bytes
-        with torch.cuda.device(dev):
-            _lib.check(lib.kpgnn_hop_mlp_bwd(ctypes.byref(d), _stream(s)), "kpgnn_hop_mlp_bwd")
+        _lib.launch("kpgnn_hop_mlp_bwd", dev, ctypes.byref(d))
         parts = list(torch.split(gflat, sizes))
         gth = parts[4].view(K, DO) if theta is not None else None
         gwc = parts[-2].view(H, DO) if H else None
@@ -716,12 +700,10 @@ class GeoTheta(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, alphas, K):
-        lib = _lib.load()
         alphas = alphas.contiguous()
         D = alphas.numel()
         theta = torch.empty((K, D), dtype=torch.float32, device=alphas.device)
-        with torch.cuda.device(alphas.device):
-            _lib.check(lib.kpgnn_geo_theta_fwd(alphas.data_ptr(), K, D, theta.data_ptr(), _stream(alphas)), "kpgnn_geo_theta_fwd")
+        _lib.launch("kpgnn_geo_theta_fwd", alphas.device, alphas.data_ptr(), K, D, theta.data_ptr())
         ctx.save_for_backward(alphas, theta)
         ctx.K = K
         return theta
@@ -729,13 +711,11 @@ class GeoTheta(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gtheta):
         alphas, theta = ctx.saved_tensors
-        lib = _lib.load()
         gtheta = gtheta.contiguous()
         D = alphas.numel()
         ga = torch.empty_like(alphas)
-        with torch.cuda.device(alphas.device):
-            _lib.check(lib.kpgnn_geo_theta_bwd(alphas.data_ptr(), theta.data_ptr(), gtheta.data_ptr(), ctx.K, D, ga.data_ptr(),
-                                               _stream(alphas)), "kpgnn_geo_theta_bwd")
+        _lib.launch("kpgnn_geo_theta_bwd", alphas.device,
+                    alphas.data_ptr(), theta.data_ptr(), gtheta.data_ptr(), ctx.K, D, ga.data_ptr())
         return ga, None
 
 
@@ -754,9 +734,7 @@ class ScoreHead(torch.autograd.Function):
         w = weight.reshape(-1).contiguous()
         G, D = p.shape
         score = torch.empty((G, 1), dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            _lib.check(_lib.load().kpgnn_score_head_fwd(p.data_ptr(), w.data_ptr(), _ptr(bias), G, D, score.data_ptr(), _stream(p)),
-                       "kpgnn_score_head_fwd")
+        _lib.launch("kpgnn_score_head_fwd", p.device, p.data_ptr(), w.data_ptr(), _ptr(bias), G, D, score.data_ptr())
         ctx.save_for_backward(p, w)
         ctx.has_bias = bias is not None
         return score
@@ -769,9 +747,8 @@ class ScoreHead(torch.autograd.Function):
         dp_ = torch.empty_like(p) if ctx.needs_input_grad[0] else None
         dw = torch.empty((1, D), dtype=torch.float32, device=p.device)
         db = torch.empty(1, dtype=torch.float32, device=p.device) if ctx.has_bias else None
-        with torch.cuda.device(p.device):
-            _lib.check(_lib.load().kpgnn_score_head_bwd(p.data_ptr(), w.data_ptr(), ds.data_ptr(), G, D, _ptr(dp_), dw.data_ptr(),
-                                                        _ptr(db), _stream(p)), "kpgnn_score_head_bwd")
+        _lib.launch("kpgnn_score_head_bwd", p.device,
+                    p.data_ptr(), w.data_ptr(), ds.data_ptr(), G, D, _ptr(dp_), dw.data_ptr(), _ptr(db))
         return dp_, dw, db
 
 
@@ -795,9 +772,7 @@ class RegressionLoss(torch.autograd.Function):
         assert s.numel() == t.numel() and s.dtype == torch.float32
         loss = torch.empty((), dtype=torch.float32, device=s.device)
         ds = torch.empty_like(s) if ctx.needs_input_grad[0] else None
-        with torch.cuda.device(s.device):
-            _lib.check(_lib.load().kpgnn_regression_loss(s.data_ptr(), t.data_ptr(), s.numel(), kind, loss.data_ptr(), _ptr(ds),
-                                                         _stream(s)), "kpgnn_regression_loss")
+        _lib.launch("kpgnn_regression_loss", s.device, s.data_ptr(), t.data_ptr(), s.numel(), kind, loss.data_ptr(), _ptr(ds))
         ctx.save_for_backward(ds)
         ctx.shape = score.shape
         return loss
@@ -817,9 +792,8 @@ def regression_loss_and_grad(score, y, kind="l1"):
         assert s.is_cuda and s.dtype == torch.float32 and s.numel() == t.numel() and s.numel() >= 1
         loss = torch.empty((), dtype=torch.float32, device=s.device)
         ds = torch.empty_like(s)
-        with torch.cuda.device(s.device):
-            _lib.check(_lib.load().kpgnn_regression_loss(s.data_ptr(), t.data_ptr(), s.numel(), 0 if kind == "l1" else 1,
-                                                         loss.data_ptr(), ds.data_ptr(), _stream(s)), "kpgnn_regression_loss")
+        _lib.launch("kpgnn_regression_loss", s.device,
+                    s.data_ptr(), t.data_ptr(), s.numel(), 0 if kind == "l1" else 1, loss.data_ptr(), ds.data_ptr())
     return loss, ds.view(score.shape)
 
 
