@@ -12,7 +12,6 @@ namespace kpgnn {
 namespace {
 
 constexpr int kBlock = 256;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 __device__ __forceinline__ float sigm(float x) { return __frcp_rn(1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanh_(float x) { return 2.0f * sigm(2.0f * x) - 1.0f; }
@@ -312,12 +311,7 @@ __global__ void __launch_bounds__(kScanThreads) attn_scan_fwd_kernel(const ScanP
             const bf3_x8 bl = __builtin_bit_cast(bf3_x8, make_uint4(bf3_pack(l0.x, l0.y), bf3_pack(l1.x, l1.y), bf3_pack(l2.x, l2.y), bf3_pack(l3.x, l3.y)));
             const bf3_x8 ah = __builtin_bit_cast(bf3_x8, wl[dir][ks][0][lane]), am = __builtin_bit_cast(bf3_x8, wl[dir][ks][1][lane]),
                          al = __builtin_bit_cast(bf3_x8, wl[dir][ks][2][lane]);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);                  // smallest terms first
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+            bf3_mma6(acc, ah, am, al, bh, bm, bl);
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
@@ -533,12 +527,7 @@ __global__ void __launch_bounds__(256) attn_dx_kernel(const DxParams p) {
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const bf3_x8 bh = ld8(bp + 32 * ks), bm = ld8(bp + 32 * kDxPk + 32 * ks), bl = ld8(bp + 64 * kDxPk + 32 * ks);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][2], bh, acc, 0, 0, 0);          // smallest terms first
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][0], bl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][1], bm, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][1], bh, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][0], bm, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][0], bh, acc, 0, 0, 0);
+            bf3_mma6(acc, wa[ks][0], wa[ks][1], wa[ks][2], bh, bm, bl);
         }
         const int64_t r = tile * 32 + row;
         if (r < p.R) {

@@ -14,7 +14,7 @@
 // accumulator register r of lane l is C[m = 4 * (l >> 4) + r][n = l & 15].
 // Weight-gradient tiles stay in accumulators for the whole launch; per-block partials go to a slab that is added
 // in block order (deterministic).
-#include "kpgnn_common.h"
+#include "mfma_tile.h"
 
 namespace kpgnn {
 namespace {
@@ -591,7 +591,7 @@ int hm_plan(int64_t N, int K, int DI, int DO, int H, bool theta, HmPlan* pl) {
         return fail(KPGNN_ELIMIT, "hop_mlp: K*D=%lld exceeds %d", (long long)K * D, kMaxCols * kHmThreads);
     int v = K * D;
     if (H > v) v = H;
-    pl->LD = v + ((4 - v % 8) + 8) % 8;                      // pitch = 4 (mod 8)
+    pl->LD = mfma_pitch(v);
     int Hp = (H + 15) & ~15;
     if (Hp % 32 == 0) Hp += 16;                              // pitch = 16 (mod 32): the 4 k-rows of a B read are 16 banks apart
     pl->Hp = H ? Hp : 0;

@@ -34,11 +34,9 @@
 // 4 columns (thread t -> column group t % (C/4), row lane t / (C/4)), so per-column coefficients and partial sums
 // live in registers and a tile is still one contiguous, coalesced run of float4s.
 #pragma once
-#include "kpgnn_common.h"
+#include "mfma_tile.h"
 
 namespace kpgnn {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 struct LinFParams {
     const int32_t* n_dyn;
@@ -58,38 +56,19 @@ struct LinFParams {
     const float* e_x; const float* e_mean; const float* e_invstd; const float* e_gamma; const float* e_beta;   // EPI 2
 };
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
+// ---- The BatchNorm arithmetic of the PRO / EPI variants: the one copy, used by lin_fused_kernel below and by lin3f_kernel
+// (linear_bf3_fused.hip).
+// Coefficient rows in LDS, one value per column: cin[12][I] = mean, invstd, gamma, beta | PRO >= 2: ai = gamma * invstd,
+// k0 = ai * s0 / N, k1 = ai * s1 / N | PRO 3, the outer norm: mean, invstd, ao = gamma * invstd, q0 = ao * s0o / N,
+// q1 = ao * s1o / N; cout[4][O] (EPI 2) = mean, invstd, gamma, beta of the previous BatchNorm.
+constexpr int kLinCinRows = 12, kLinCoutRows = 4;
 
-template <int KS, int M, int PRO, int EPI>
-__global__ void __launch_bounds__(256, 2)
-lin_fused_kernel(LinFParams p) {
-    p.N = live_rows(p.N, p.n_dyn);
-    if (p.N <= 0) return;                             // (only under a dynamic count of zero)
-    extern __shared__ __attribute__((aligned(16))) float xl[];      // [32*M][pitch] tile, then the coefficient rows
-    constexpr int ROWS = 32 * M;
-    constexpr int I = 2 * KS, CGI = I / 4, RLI = 256 / CGI, NAI = CGI * RLI, PFI = (ROWS + RLI - 1) / RLI;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int kk = lane >> 5, c = lane & 31;
-    const int O = p.O, pitch = p.pitch;
-    float* cin = xl + ROWS * pitch;                   // PRO coefficients: [12][I] (rows 7..11: PRO 3's outer norm)
-    float* cout = cin + 12 * I;                       // EPI 2 coefficients: [4][O]
-    const int o = wave * 32 + c;
-    // this wave's strip of the weight as MFMA A-fragments: a[ks] = W[o][2 ks + kk]
-    float a[KS];
-    if (p.wt) {                                       // w is [I][O]: lanes run along o, coalesced as is
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) a[ks] = o < O ? p.w[(int64_t)(2 * ks + kk) * O + o] : 0.f;
-    } else {                                          // w is [O][I]: every lane streams ITS row 16 B at a time
-#pragma unroll
-        for (int j = 0; j < KS / 2; ++j) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (o < O) v = ld4(p.w + (int64_t)o * I + 4 * j);
-            a[2 * j] = kk ? v.y : v.x;
-            a[2 * j + 1] = kk ? v.w : v.z;
-        }
-    }
-    // ---- per-column coefficients (every block finishes the statistics it consumes from the slot)
+// Every block finishes the statistics it consumes from the slot (threads tid < I, tid < O); block 0 publishes what the launch
+// owes the caller: PRO 1 in_mean / in_invstd and the running statistics, PRO 2 / 3 dgamma / dbeta (PRO 3: of both norms).
+// The caller synchronises the block afterwards.
+template <int PRO, int EPI>
+__device__ __forceinline__ void lin_bn_coefficients(const LinFParams& p, float* cin, int I, int O, int tid) {
+    float* cout = cin + kLinCinRows * I;              // (the output-side rows follow the input-side ones)
     if (PRO == 1 && tid < I) {
         const double inv_n = 1.0 / (double)p.N;
         const double m1 = slot_sum(p.in_slot, I, 0, tid) * inv_n;
@@ -144,6 +123,60 @@ lin_fused_kernel(LinFParams p) {
     if (EPI == 2 && tid < O) {
         cout[tid] = p.e_mean[tid]; cout[O + tid] = p.e_invstd[tid]; cout[2 * O + tid] = p.e_gamma[tid]; cout[3 * O + tid] = p.e_beta[tid];
     }
+}
+
+// The per-element BatchNorm arithmetic of both kernels.  Macros, not functions: they expand where the column coefficients of a
+// thread's group of 4 columns are float4 locals named after their rows (mean, istd, g, bt, ai, k0, k1; PRO 3: om, oi, ao, q0,
+// q1).  As functions (over a struct of the coefficients, with or without the row-tail flag) they changed the instruction
+// schedule and the register allocation of the fp32 kernel's PRO 2 / 3 variants; EPI 2's three-line mask stays in each kernel.
+// PRO 1: x' = (x - mean) * invstd * gamma + beta on a float4 (the caller applies the ReLU)
+#define KPGNN_BN_AFFINE(v)                                                                                          \
+    v.x = fmaf((v.x - mean.x) * istd.x, g.x, bt.x); v.y = fmaf((v.y - mean.y) * istd.y, g.y, bt.y);                \
+    v.z = fmaf((v.z - mean.z) * istd.z, g.z, bt.z); v.w = fmaf((v.w - mean.w) * istd.w, g.w, bt.w);
+
+// PRO 2 / 3, component f of a float4: r = dy from DZ (PRO 3: from dh, through the outer norm first) and the saved forward input
+// XS of the inner norm
+#define KPGNN_BN_BWD1(PRO, RELU, DZ, XS, f, r)                              \
+    const float xh = (XS.f - mean.f) * istd.f;                             \
+    float d = DZ.f;                                                        \
+    const float pre = fmaf(xh, g.f, bt.f);                                 \
+    if (PRO == 3) {                                                        \
+        const float zz = (RELU && pre <= 0.f) ? 0.f : pre;                 \
+        const float xo = (zz - om.f) * oi.f;                               \
+        d = fmaf(-xo, q1.f, fmaf(ao.f, d, -q0.f));                         \
+    }                                                                      \
+    if (RELU && pre <= 0.f) d = 0.f;                                       \
+    const float r = fmaf(-xh, k1.f, fmaf(ai.f, d, -k0.f));
+
+template <int KS, int M, int PRO, int EPI>
+__global__ void __launch_bounds__(256, 2)
+lin_fused_kernel(LinFParams p) {
+    p.N = live_rows(p.N, p.n_dyn);
+    if (p.N <= 0) return;                             // (only under a dynamic count of zero)
+    extern __shared__ __attribute__((aligned(16))) float xl[];      // [32*M][pitch] tile, then the coefficient rows
+    constexpr int ROWS = 32 * M;
+    constexpr int I = 2 * KS, CGI = I / 4, RLI = 256 / CGI, NAI = CGI * RLI, PFI = (ROWS + RLI - 1) / RLI;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int kk = lane >> 5, c = lane & 31;
+    const int O = p.O, pitch = p.pitch;
+    float* cin = xl + ROWS * pitch;                   // PRO coefficients
+    float* cout = cin + kLinCinRows * I;              // EPI 2 coefficients
+    const int o = wave * 32 + c;
+    // this wave's strip of the weight as MFMA A-fragments: a[ks] = W[o][2 ks + kk]
+    float a[KS];
+    if (p.wt) {                                       // w is [I][O]: lanes run along o, coalesced as is
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) a[ks] = o < O ? p.w[(int64_t)(2 * ks + kk) * O + o] : 0.f;
+    } else {                                          // w is [O][I]: every lane streams ITS row 16 B at a time
+#pragma unroll
+        for (int j = 0; j < KS / 2; ++j) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (o < O) v = ld4(p.w + (int64_t)o * I + 4 * j);
+            a[2 * j] = kk ? v.y : v.x;
+            a[2 * j + 1] = kk ? v.w : v.z;
+        }
+    }
+    lin_bn_coefficients<PRO, EPI>(p, cin, I, O, tid);
     if (PRO != 0 || EPI == 2) __syncthreads();
     // ---- input side: thread -> (column group, row lane); a tile is one contiguous run of NAI float4s per row-lane step
     const int cgi = tid % CGI, rli = tid / CGI;
@@ -173,8 +206,7 @@ lin_fused_kernel(LinFParams p) {
             if (act_i && rli + j * RLI < ROWS) {
                 float4 v = pf[j];
                 if (PRO == 1) {
-                    v.x = fmaf((v.x - mean.x) * istd.x, g.x, bt.x); v.y = fmaf((v.y - mean.y) * istd.y, g.y, bt.y);
-                    v.z = fmaf((v.z - mean.z) * istd.z, g.z, bt.z); v.w = fmaf((v.w - mean.w) * istd.w, g.w, bt.w);
+                    KPGNN_BN_AFFINE(v)
                     if (p.pro_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                 }
                 st4(xl + (rli + j * RLI) * pitch + 4 * cgi, v);
@@ -204,13 +236,7 @@ lin_fused_kernel(LinFParams p) {
             if (act_i && rli + j * RLI < ROWS) {
                 float4 v;
                 const bool in = r0 + rli + j * RLI < p.N;
-#define KP_BWD1(f) { const float xh = (xs[j].f - mean.f) * istd.f; float d = dz[j].f; \
-                     const float pre = fmaf(xh, g.f, bt.f); \
-                     if (PRO == 3) { const float zz = (p.pro_relu && pre <= 0.f) ? 0.f : pre; \
-                                     const float xo = (zz - om.f) * oi.f; \
-                                     d = fmaf(-xo, q1.f, fmaf(ao.f, d, -q0.f)); } \
-                     if (p.pro_relu && pre <= 0.f) d = 0.f; \
-                     v.f = in ? fmaf(-xh, k1.f, fmaf(ai.f, d, -k0.f)) : 0.f; }
+#define KP_BWD1(f) { KPGNN_BN_BWD1(PRO, p.pro_relu, dz[j], xs[j], f, r) v.f = in ? r : 0.f; }
                 KP_BWD1(x) KP_BWD1(y) KP_BWD1(z) KP_BWD1(w)
 #undef KP_BWD1
                 st4(xl + (rli + j * RLI) * pitch + 4 * cgi, v);
@@ -326,24 +352,17 @@ lin_fused_kernel(LinFParams p) {
 
 struct LinLaunch { int m; unsigned grid; size_t lds; int pitch; };
 
-// Tile rows (32 * m, the smallest that makes the launch one round over two blocks per CU), grid, LDS bytes and the row
-// pitch (= 4 mod 8 floats: 16-B aligned rows, conflict-free 16-B accesses) shared by the x and the y view of the buffer.
+// Tile rows, grid (two blocks per CU; mfma_tile.h), LDS bytes and the row pitch shared by the x and the y view of the buffer.
 inline LinLaunch lin_plan(int64_t N, int O, int I) {
     LinLaunch L;
-    const int wmax = I > O ? I : O;
-    L.pitch = wmax + ((4 - wmax % 8) + 8) % 8;
-    const int64_t slots = (int64_t)device_facts().cu_count * 2;
-    int m = (int)((N + slots * 32 - 1) / (slots * 32));
-    L.m = m < 1 ? 1 : (m > 3 ? 3 : m);
-    const int rows = 32 * L.m;
-    // tile + 12 input-side + 4 output-side coefficient rows; the fp64 block reduction of the statistics reuses the tile
-    size_t fl = (size_t)rows * L.pitch + 12 * (size_t)I + 4 * (size_t)O;
+    L.pitch = mfma_pitch(I > O ? I : O);
+    const TilePlan t = tile_plan(N, (int64_t)device_facts().cu_count * 2, {1, 2, 3}, true);
+    L.m = t.m; L.grid = t.grid;
+    // tile + the coefficient rows; the fp64 block reduction of the statistics reuses the tile
+    size_t fl = (size_t)t.rows * L.pitch + kLinCinRows * (size_t)I + kLinCoutRows * (size_t)O;
     const size_t red = 2 * (size_t)(256 / (O / 4)) * 2 * O;      // doubles, counted in floats
     if (fl < red) fl = red;
     L.lds = sizeof(float) * fl;
-    const int64_t tiles = (N + rows - 1) / rows;
-    const int64_t cap = L.m == 1 ? slots * 2 : slots;
-    L.grid = (unsigned)(cap < tiles ? cap : tiles);
     return L;
 }
 
@@ -352,35 +371,39 @@ int lin_fused_launch(const LinFParams& p, hipStream_t s) {
     const LinLaunch L = lin_plan(p.N, p.O, p.I);
     LinFParams q = p;
     q.pitch = L.pitch;
-    dim3 blk(256);
-#define KP_LF2(KSV, MV) do { \
-        KPGNN_HIP_TRY(ensure_dynamic_lds((const void*)lin_fused_kernel<KSV, MV, PRO, EPI>, L.lds)); \
-        hipLaunchKernelGGL((lin_fused_kernel<KSV, MV, PRO, EPI>), dim3(L.grid), blk, L.lds, s, q); } while (0)
-#define KP_LF(KSV) do { if (L.m == 1) KP_LF2(KSV, 1); else if (L.m == 2) KP_LF2(KSV, 2); else KP_LF2(KSV, 3); } while (0)
-    switch (p.I) {
-        case 32: KP_LF(16); break;
-        case 64: KP_LF(32); break;
-        case 96: KP_LF(48); break;
-        case 104: KP_LF(52); break;
-        case 128: KP_LF(64); break;
-        default: return fail(KPGNN_ELIMIT, "linear: I=%d is not one of 32, 64, 96, 104, 128 (the k-loop is fully unrolled)", p.I);
-    }
-#undef KP_LF
-#undef KP_LF2
+    const int rc = LinWidths::dispatch(p.I, "linear_bn", [&](auto KS) {
+        auto go = [&](auto M) {
+            KPGNN_HIP_TRY(ensure_dynamic_lds((const void*)lin_fused_kernel<KS(), M(), PRO, EPI>, L.lds));
+            hipLaunchKernelGGL((lin_fused_kernel<KS(), M(), PRO, EPI>), dim3(L.grid), dim3(256), L.lds, s, q);
+            return (int)KPGNN_OK;
+        };
+        return L.m == 1 ? go(std::integral_constant<int, 1>{}) : L.m == 2 ? go(std::integral_constant<int, 2>{}) : go(std::integral_constant<int, 3>{});
+    });
+    if (rc != KPGNN_OK) return rc;
     KPGNN_LAUNCH_CHECK("lin_fused_kernel");
     return KPGNN_OK;
 }
 
-inline bool lin_supported_width(int I) { return I == 32 || I == 64 || I == 96 || I == 104 || I == 128; }
-
-// one explicit instantiation set per translation unit (lin_fused_*.hip), so that the five variants compile in parallel
-int lin_launch_plain(const LinFParams& p, hipStream_t s);       // PRO 0, EPI 0
-int lin_launch_stats(const LinFParams& p, hipStream_t s);       // PRO 0, EPI 1
-int lin_launch_bn_stats(const LinFParams& p, hipStream_t s);    // PRO 1, EPI 1
-int lin_launch_bn(const LinFParams& p, hipStream_t s);          // PRO 1, EPI 0
-int lin_launch_bwd_reduce(const LinFParams& p, hipStream_t s);  // PRO 2, EPI 2
-int lin_launch_bwd(const LinFParams& p, hipStream_t s);         // PRO 2, EPI 0
-int lin_launch_bwd2_reduce(const LinFParams& p, hipStream_t s); // PRO 3, EPI 2
+// The one table of instantiated (PRO, EPI) pairs: f(std::integral_constant<int, PRO>, std::integral_constant<int, EPI>)
+// launches its kernel and returns the status.
+template <typename F>
+int dispatch_pro_epi(int pro, int epi, const char* who, F&& f) {
+#define KPGNN_PE_CASE(P, E) case P * 10 + E: return f(std::integral_constant<int, P>{}, std::integral_constant<int, E>{});
+    switch (pro * 10 + epi) {
+        KPGNN_PE_CASE(0, 0) KPGNN_PE_CASE(0, 1) KPGNN_PE_CASE(1, 0) KPGNN_PE_CASE(1, 1)
+        KPGNN_PE_CASE(2, 0) KPGNN_PE_CASE(2, 2) KPGNN_PE_CASE(3, 2)
+    }
+#undef KPGNN_PE_CASE
+    return fail(KPGNN_ELIMIT, "%s: combination pro=%d epi=%d is not instantiated", who, pro, epi);
+}
+// each pair is instantiated in a translation unit of its own (lin_fused_*.hip): the fully unrolled k-loops compile in parallel
+extern template int lin_fused_launch<0, 0>(const LinFParams&, hipStream_t);
+extern template int lin_fused_launch<0, 1>(const LinFParams&, hipStream_t);
+extern template int lin_fused_launch<1, 0>(const LinFParams&, hipStream_t);
+extern template int lin_fused_launch<1, 1>(const LinFParams&, hipStream_t);
+extern template int lin_fused_launch<2, 0>(const LinFParams&, hipStream_t);
+extern template int lin_fused_launch<2, 2>(const LinFParams&, hipStream_t);
+extern template int lin_fused_launch<3, 2>(const LinFParams&, hipStream_t);
 // linear_bf3_fused.hip: the same launches on the bf16 matrix cores (wfrag: linear3_split_w's copy of W)
 int linear3_fused(const LinFParams& p, int pro, int epi, const uint4* wfrag, hipStream_t s);
 

@@ -1,6 +1,4 @@
 // One variant of lin_fused_kernel (lin_fused.h) per translation unit: the fully unrolled k-loops compile in parallel.
 #include "lin_fused.h"
 
-namespace kpgnn {
-int lin_launch_bn(const LinFParams& p, hipStream_t s) { return lin_fused_launch<1, 0>(p, s); }
-}  // namespace kpgnn
+template int kpgnn::lin_fused_launch<1, 0>(const kpgnn::LinFParams&, hipStream_t);

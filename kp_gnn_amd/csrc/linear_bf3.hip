@@ -146,13 +146,7 @@ lin3_kernel(const L3Params p) {
                 float4 x = v[i];
                 if (masked) { x.x = mk[i].x > 0.f ? x.x : 0.f; x.y = mk[i].y > 0.f ? x.y : 0.f; x.z = mk[i].z > 0.f ? x.z : 0.f; x.w = mk[i].w > 0.f ? x.w : 0.f; }
                 if (tail && prow[i] > lim) x = make_float4(0.f, 0.f, 0.f, 0.f);       // (rows beyond N stay zero)
-                bf3_u2 h0, m0, l0, h1, m1, l1;
-                bf3_split2(bf3_f2{x.x, x.y}, h0, m0, l0);
-                bf3_split2(bf3_f2{x.z, x.w}, h1, m1, l1);
-                __bf16* q = buf + prow[i] * PK + 4 * pcg[i];
-                *reinterpret_cast<uint2*>(q) = make_uint2(bf3_pack(h0.x, h0.y), bf3_pack(h1.x, h1.y));
-                *reinterpret_cast<uint2*>(q + ROWS * PK) = make_uint2(bf3_pack(m0.x, m0.y), bf3_pack(m1.x, m1.y));
-                *reinterpret_cast<uint2*>(q + 2 * ROWS * PK) = make_uint2(bf3_pack(l0.x, l0.y), bf3_pack(l1.x, l1.y));
+                bf3_store_planes(buf, prow[i], PK, 4 * pcg[i], ROWS * PK, x);
             }
         };
         __builtin_amdgcn_s_setprio(2);
@@ -183,7 +177,6 @@ lin3_kernel(const L3Params p) {
     }
 
     // ---- multiplying waves: output columns [32 wave, 32 wave + 32)
-    typedef __attribute__((ext_vector_type(16))) float f32x16;
     const int n = wave * 32 + c;
     const bool strip = wave * 32 < O;                 // (uniform)
     const uint4* wf = p.wfrag + (int64_t)wave * KS * 192 + lane;           // this wave's strip; a state's strips are 4 KS 192 items apart
@@ -250,12 +243,7 @@ lin3_kernel(const L3Params p) {
                         const __bf16* np = ap + (j % kL3Tiles) * 32 * PK + 16 * (j / kL3Tiles);
                         nh = ld8(np); nm = ld8(np + ROWS * PK); nl = ld8(np + 2 * ROWS * PK);
                     }
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, b0[0], acc[m], 0, 0, 0);      // smallest terms first
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, b0[2], acc[m], 0, 0, 0);
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, b0[1], acc[m], 0, 0, 0);
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, b0[0], acc[m], 0, 0, 0);
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, b0[1], acc[m], 0, 0, 0);
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, b0[0], acc[m], 0, 0, 0);
+                    bf3_mma6(acc[m], ah, am, al, b0[0], b0[1], b0[2]);
                     // (the next fragments' LDS reads FIRST, then the six matrix instructions: left alone the scheduler sinks the reads
                     //  to the end of the group and the next group starts by waiting out their latency - 88 cycles per instruction)
                     __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);

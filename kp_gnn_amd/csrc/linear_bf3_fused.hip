@@ -29,67 +29,13 @@ lin3f_kernel(LinFParams p, const uint4* __restrict__ wfrag) {
     constexpr int NCG = 4 * KS, RLMIN = 256 / NCG;   // float4 column groups of a row (upper bound), row lanes of the staging waves
     constexpr int PF = (ROWS + RLMIN - 1) / RLMIN;   // rows per staging thread and group
     __bf16* pl = reinterpret_cast<__bf16*>(f3_lds);
-    float* cin = reinterpret_cast<float*>(pl + 2 * BUF);       // PRO coefficients: [12][I]
+    float* cin = reinterpret_cast<float*>(pl + 2 * BUF);       // PRO coefficients
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kg = lane >> 5, c = lane & 31;
     const int O = p.O, I = p.I;
-    float* cout = cin + 12 * I;                                // EPI 2 coefficients: [4][O]
-    // ---- per-column coefficients (every block finishes the statistics it consumes from the slot)
-    if (PRO == 1 && tid < I) {
-        const double inv_n = 1.0 / (double)p.N;
-        const double m1 = slot_sum(p.in_slot, I, 0, tid) * inv_n;
-        double var = slot_sum(p.in_slot, I, 1, tid) * inv_n - m1 * m1;
-        if (var < 0.0) var = 0.0;
-        const float mean = (float)m1, istd = (float)(1.0 / sqrt(var + (double)p.in_eps));
-        cin[tid] = mean; cin[I + tid] = istd; cin[2 * I + tid] = p.in_gamma[tid]; cin[3 * I + tid] = p.in_beta[tid];
-        if (blockIdx.x == 0) {
-            p.in_mean[tid] = mean; p.in_invstd[tid] = istd;
-            if (p.rmean) {
-                const double unb = p.N > 1 ? var * (double)p.N / (double)(p.N - 1) : var;
-                p.rmean[tid] = (1.f - p.momentum) * p.rmean[tid] + p.momentum * mean;
-                p.rvar[tid] = (1.f - p.momentum) * p.rvar[tid] + p.momentum * (float)unb;
-            }
-            if (tid == 0 && p.nbt) *p.nbt += 1;
-        }
-    }
-    if (PRO == 2 && tid < I) {
-        const double inv_n = 1.0 / (double)p.N;
-        const double s0 = slot_sum(p.in_slot, I, 0, tid), s1 = slot_sum(p.in_slot, I, 1, tid);
-        const float mean = p.in_mean[tid], istd = p.in_invstd[tid], g = p.in_gamma[tid];
-        const float ai = g * istd;
-        cin[tid] = mean; cin[I + tid] = istd; cin[2 * I + tid] = g; cin[3 * I + tid] = p.in_beta[tid];
-        cin[4 * I + tid] = ai; cin[5 * I + tid] = ai * (float)(s0 * inv_n); cin[6 * I + tid] = ai * (float)(s1 * inv_n);
-        if (blockIdx.x == 0) { p.dbeta[tid] = (float)s0; p.dgamma[tid] = (float)s1; }
-    }
-    if (PRO == 3 && tid < I) {
-        const double inv_n = 1.0 / (double)p.N;
-        double t[8];
-#pragma unroll
-        for (int n = 0; n < 8; ++n) {
-            double a = 0.0;
-#pragma unroll
-            for (int r = 0; r < KPGNN_STAT_REPLICAS; ++r) a += p.in_slot[((int64_t)r * 8 + n) * I + tid];
-            t[n] = a;
-        }
-        const float mean = p.in_mean[tid], istd = p.in_invstd[tid], g = p.in_gamma[tid];
-        const float om = p.o_mean[tid], oi = p.o_invstd[tid];
-        const float ai = g * istd, ao = p.o_gamma[tid] * oi;
-        const double m0 = t[0] * inv_n, m1 = t[1] * inv_n;                  // outer: s0/N, s1/N
-        const double s0 = (double)ao * (t[2] - m0 * t[3] - m1 * t[4]);        // inner: sum dzm
-        const double s1 = (double)ao * (t[5] - m0 * t[6] - m1 * t[7]);        //        sum dzm * xhat_in
-        cin[tid] = mean; cin[I + tid] = istd; cin[2 * I + tid] = g; cin[3 * I + tid] = p.in_beta[tid];
-        cin[4 * I + tid] = ai; cin[5 * I + tid] = ai * (float)(s0 * inv_n); cin[6 * I + tid] = ai * (float)(s1 * inv_n);
-        cin[7 * I + tid] = om; cin[8 * I + tid] = oi; cin[9 * I + tid] = ao;
-        cin[10 * I + tid] = ao * (float)m0; cin[11 * I + tid] = ao * (float)m1;
-        if (blockIdx.x == 0) {
-            p.dbeta[tid] = (float)s0; p.dgamma[tid] = (float)s1;
-            p.o_dbeta[tid] = (float)t[0]; p.o_dgamma[tid] = (float)t[1];
-        }
-    }
-    if (EPI == 2 && tid < O) {
-        cout[tid] = p.e_mean[tid]; cout[O + tid] = p.e_invstd[tid]; cout[2 * O + tid] = p.e_gamma[tid]; cout[3 * O + tid] = p.e_beta[tid];
-    }
+    float* cout = cin + kLinCinRows * I;                       // EPI 2 coefficients
+    lin_bn_coefficients<PRO, EPI>(p, cin, I, O, tid);
     for (int i = tid; i < 2 * BUF / 8; i += 512) f3_lds[i] = make_uint4(0u, 0u, 0u, 0u);       // (the k padding stays zero)
     __syncthreads();
     const int64_t groups = (p.N + ROWS - 1) / ROWS;
@@ -122,14 +68,14 @@ lin3f_kernel(LinFParams p, const uint4* __restrict__ wfrag) {
                 if (PRO >= 2) pu[i] = *reinterpret_cast<const float4*>(up + off);
             }
         };
-        auto commit = [&](int g, float4 (&pv)[PF], float4 (&pu)[PF]) {
-            if (g >= G) return;                                   // (uniform; no request inside)
-            const int64_t r0 = ((int64_t)blockIdx.x + (int64_t)g * gridDim.x) * ROWS;
+        auto commit = [&](int gi, float4 (&pv)[PF], float4 (&pu)[PF]) {
+            if (gi >= G) return;                                   // (uniform; no request inside)
+            const int64_t r0 = ((int64_t)blockIdx.x + (int64_t)gi * gridDim.x) * ROWS;
             const int lim = (int)min((int64_t)ROWS - 1, p.N - 1 - r0);
-            __bf16* buf = pl + (g & 1) * BUF;
+            __bf16* buf = pl + (gi & 1) * BUF;
             char* tp = PRO >= 2 ? reinterpret_cast<char*>(p.xt + r0 * I) : nullptr;
-            float4 mean, istd, gm, bt, ai, k0, k1, om, oi, ao, q0, q1;
-            if (PRO >= 1) { mean = ld4(cin + 4 * cg); istd = ld4(cin + I + 4 * cg); gm = ld4(cin + 2 * I + 4 * cg); bt = ld4(cin + 3 * I + 4 * cg); }
+            float4 mean, istd, g, bt, ai, k0, k1, om, oi, ao, q0, q1;
+            if (PRO >= 1) { mean = ld4(cin + 4 * cg); istd = ld4(cin + I + 4 * cg); g = ld4(cin + 2 * I + 4 * cg); bt = ld4(cin + 3 * I + 4 * cg); }
             if (PRO >= 2) { ai = ld4(cin + 4 * I + 4 * cg); k0 = ld4(cin + 5 * I + 4 * cg); k1 = ld4(cin + 6 * I + 4 * cg); }
             if (PRO == 3) { om = ld4(cin + 7 * I + 4 * cg); oi = ld4(cin + 8 * I + 4 * cg); ao = ld4(cin + 9 * I + 4 * cg);
                             q0 = ld4(cin + 10 * I + 4 * cg); q1 = ld4(cin + 11 * I + 4 * cg); }
@@ -137,32 +83,18 @@ lin3f_kernel(LinFParams p, const uint4* __restrict__ wfrag) {
             for (int i = 0; i < PF; ++i) {
                 float4 v = pv[i];
                 if (PRO == 1) {
-                    v.x = fmaf((v.x - mean.x) * istd.x, gm.x, bt.x); v.y = fmaf((v.y - mean.y) * istd.y, gm.y, bt.y);
-                    v.z = fmaf((v.z - mean.z) * istd.z, gm.z, bt.z); v.w = fmaf((v.w - mean.w) * istd.w, gm.w, bt.w);
+                    KPGNN_BN_AFFINE(v)
                     if (p.pro_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                 }
                 if (PRO >= 2) {
-                    const float4 dz = pv[i], xs = pu[i];
-#define KP_BWD1(f) { const float xh = (xs.f - mean.f) * istd.f; float d = dz.f; \
-                     const float pre = fmaf(xh, gm.f, bt.f); \
-                     if (PRO == 3) { const float zz = (p.pro_relu && pre <= 0.f) ? 0.f : pre; \
-                                     const float xo = (zz - om.f) * oi.f; \
-                                     d = fmaf(-xo, q1.f, fmaf(ao.f, d, -q0.f)); } \
-                     if (p.pro_relu && pre <= 0.f) d = 0.f; \
-                     v.f = fmaf(-xh, k1.f, fmaf(ai.f, d, -k0.f)); }
+#define KP_BWD1(f) { KPGNN_BN_BWD1(PRO, p.pro_relu, pv[i], pu[i], f, r) v.f = r; }
                     KP_BWD1(x) KP_BWD1(y) KP_BWD1(z) KP_BWD1(w)
 #undef KP_BWD1
                     // (the transformed rows leave for the weight-gradient kernel; repeated tasks store the same bytes again)
                     *reinterpret_cast<float4*>(tp + __umul24((uint32_t)min(prow[i], lim), sbytes) + 16u * (uint32_t)cg) = v;
                 }
                 if (prow[i] > lim) v = make_float4(0.f, 0.f, 0.f, 0.f);               // (rows beyond N stay zero)
-                bf3_u2 h0, m0, l0, h1, m1, l1;
-                bf3_split2(bf3_f2{v.x, v.y}, h0, m0, l0);
-                bf3_split2(bf3_f2{v.z, v.w}, h1, m1, l1);
-                __bf16* q = buf + prow[i] * PK + 4 * cg;
-                *reinterpret_cast<uint2*>(q) = make_uint2(bf3_pack(h0.x, h0.y), bf3_pack(h1.x, h1.y));
-                *reinterpret_cast<uint2*>(q + ROWS * PK) = make_uint2(bf3_pack(m0.x, m0.y), bf3_pack(m1.x, m1.y));
-                *reinterpret_cast<uint2*>(q + 2 * ROWS * PK) = make_uint2(bf3_pack(l0.x, l0.y), bf3_pack(l1.x, l1.y));
+                bf3_store_planes(buf, prow[i], PK, 4 * cg, ROWS * PK, v);
             }
         };
         issue(0, pvs[0], pus[0]);
@@ -252,12 +184,7 @@ lin3f_kernel(LinFParams p, const uint4* __restrict__ wfrag) {
                 for (int ks = 0; ks < KS; ++ks) {
                     bf3_x8 nh = ah, nm = am, nl = al;
                     if (ks + 1 < KS) { nh = ld8(ap + 16 * (ks + 1)); nm = ld8(ap + ROWS * PK + 16 * (ks + 1)); nl = ld8(ap + 2 * ROWS * PK + 16 * (ks + 1)); }
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, wb[ks][0], acc, 0, 0, 0);      // smallest terms first
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wb[ks][2], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, wb[ks][1], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, wb[ks][0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wb[ks][1], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wb[ks][0], acc, 0, 0, 0);
+                    bf3_mma6(acc, ah, am, al, wb[ks][0], wb[ks][1], wb[ks][2]);
                     __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
                     __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
                     __builtin_amdgcn_sched_barrier(0);
@@ -323,7 +250,7 @@ int lin3f_launch(const LinFParams& p, const uint4* wfrag, hipStream_t s) {
     const int64_t groups = (p.N + kF3Rows - 1) / kF3Rows;
     const int64_t cus = (int64_t)device_facts().cu_count;
     const int64_t grid = groups < cus ? groups : cus;
-    const size_t lds = (size_t)2 * f3_buf(ks) * 2 + sizeof(float) * (12 * (size_t)p.I + 4 * (size_t)p.O);
+    const size_t lds = (size_t)2 * f3_buf(ks) * 2 + sizeof(float) * (kLinCinRows * (size_t)p.I + kLinCoutRows * (size_t)p.O);
 #define KP_F3(KSV) do { \
         KPGNN_HIP_TRY(ensure_dynamic_lds((const void*)lin3f_kernel<KSV, PRO, EPI>, lds)); \
         hipLaunchKernelGGL((lin3f_kernel<KSV, PRO, EPI>), dim3((unsigned)grid), dim3(512), lds, s, p, wfrag); } while (0)
@@ -343,16 +270,7 @@ int lin3f_launch(const LinFParams& p, const uint4* wfrag, hipStream_t s) {
 
 // The bf16-split variant of kpgnn_linear_bn: p is what the fp32 launch would get; wfrag = the split copy of W (lin3_split_w).
 int linear3_fused(const LinFParams& p, int pro, int epi, const uint4* wfrag, hipStream_t s) {
-    switch (pro * 10 + epi) {
-        case 0: return lin3f_launch<0, 0>(p, wfrag, s);
-        case 1: return lin3f_launch<0, 1>(p, wfrag, s);
-        case 10: return lin3f_launch<1, 0>(p, wfrag, s);
-        case 11: return lin3f_launch<1, 1>(p, wfrag, s);
-        case 20: return lin3f_launch<2, 0>(p, wfrag, s);
-        case 22: return lin3f_launch<2, 2>(p, wfrag, s);
-        case 32: return lin3f_launch<3, 2>(p, wfrag, s);
-        default: return fail(KPGNN_ELIMIT, "linear_bn: combination pro=%d epi=%d is not instantiated", pro, epi);
-    }
+    return dispatch_pro_epi(pro, epi, "linear_bn", [&](auto PRO, auto EPI) { return lin3f_launch<PRO(), EPI()>(p, wfrag, s); });
 }
 
 }  // namespace kpgnn

@@ -6,14 +6,11 @@
 // per step at K = L = 8, h = 104.  Here the K-loop of the GEMM runs over the S state POINTERS: a 32M-row tile of state l is
 // staged in LDS (requested one state ahead, held in registers across the MFMA phase), every wave reloads its 32 x I strip of
 // W's column block l (L2-resident) and continues the same accumulators; bias + ReLU leave with the tile.  No concat exists.
-#include "kpgnn_common.h"
+#include "mfma_tile.h"
 
 namespace kpgnn {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-__device__ __forceinline__ float4 ldg4(const float* q) { return *reinterpret_cast<const float4*>(q); }
 
 struct LgParams {
     int64_t N; const int32_t* n_dyn;
@@ -60,7 +57,7 @@ linear_group_kernel(const LgParams p) {
             if (l == i) base = p.xs[i];
 #pragma unroll
         for (int j = 0; j < PF; ++j)
-            pf[j] = ldg4(base + min(r0 + max(prow[j], 0), last) * p.xstride + 4 * pcg[j]);
+            pf[j] = ld4(base + min(r0 + max(prow[j], 0), last) * p.xstride + 4 * pcg[j]);
     };
     auto commit = [&]() {
 #pragma unroll
@@ -72,7 +69,7 @@ linear_group_kernel(const LgParams p) {
     auto load_strip = [&](int l) {
 #pragma unroll
         for (int j = 0; j < KS / 2; ++j) {
-            const float4 v = ldg4(wo + (int64_t)l * I + 4 * j);
+            const float4 v = ld4(wo + (int64_t)l * I + 4 * j);
             an[2 * j] = kk ? v.y : v.x;
             an[2 * j + 1] = kk ? v.w : v.z;
         }
@@ -122,7 +119,7 @@ linear_group_kernel(const LgParams p) {
         for (int g = 0; g < 4; ++g) {
             const int ob = wave * 32 + 8 * g + 4 * kk;
             bias4[g] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (p.bias) bias4[g] = ldg4(p.bias + (ob < O ? ob : 0));
+            if (p.bias) bias4[g] = ld4(p.bias + (ob < O ? ob : 0));
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -154,8 +151,8 @@ extern "C" int kpgnn_linear_group_fwd(const kpgnn_linear_group_desc* d, kpgnn_st
     KPGNN_REQUIRE(d != nullptr, "linear_group_fwd: NULL descriptor");
     KPGNN_REQUIRE(d->N >= 1 && d->O >= 1 && d->I >= 1 && d->group >= 1 && d->group <= 16, "linear_group_fwd: bad N=%lld O=%d I=%d group=%d",
                   (long long)d->N, d->O, d->I, d->group);
-    if (d->O > 128 || d->O % 4 != 0 || (d->I != 32 && d->I != 64 && d->I != 96 && d->I != 104 && d->I != 128))
-        return fail(KPGNN_ELIMIT, "linear_group_fwd: needs O <= 128, O %% 4 == 0 and I in {32, 64, 96, 104, 128} (the k-loop is fully unrolled)");
+    if (d->O > 128 || d->O % 4 != 0) return fail(KPGNN_ELIMIT, "linear_group_fwd: needs O <= 128, O %% 4 == 0");
+    if (!LinWidths::has(d->I)) return LinWidths::refuse(d->I, "linear_group_fwd");
     KPGNN_REQUIRE(d->w && d->y && d->x_stride >= d->I, "linear_group_fwd: NULL pointer or x_stride < I");
     auto al = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
     if (d->x_stride % 4 != 0 || !al(d->w) || !al(d->y) || (d->bias && !al(d->bias)))
@@ -172,30 +169,25 @@ extern "C" int kpgnn_linear_group_fwd(const kpgnn_linear_group_desc* d, kpgnn_st
         if (handled || rc != KPGNN_OK) return rc;
     }
     p.xstride = d->x_stride; p.w = d->w; p.bias = d->bias; p.y = d->y;
-    p.pitch = d->I + ((4 - d->I % 8) + 8) % 8;          // pitch = 4 (mod 8) floats: 16-B aligned rows, conflict-free operand reads
-    // rows per tile = 32 * m, m in {1, 2, 3, 4, 6}: the smallest that makes the launch one round over one block per CU
-    const int64_t slots = (int64_t)device_facts().cu_count;
-    int m = (int)((d->N + slots * 32 - 1) / (slots * 32));
-    m = m < 1 ? 1 : (m > 4 ? 6 : m);
-    const int rows = 32 * m;
-    const size_t lds = sizeof(float) * (size_t)rows * p.pitch;
-    const int64_t tiles = (d->N + rows - 1) / rows;
-    const int64_t grid = slots < tiles ? slots : tiles;
+    p.pitch = mfma_pitch(d->I);
+    const TilePlan t = tile_plan(d->N, (int64_t)device_facts().cu_count, {1, 2, 3, 4, 6}, false);      // one block per CU
+    const size_t lds = sizeof(float) * (size_t)t.rows * p.pitch;
     hipStream_t s = (hipStream_t)stream;
-#define KP_LG2(KSV, MV) do { \
-        KPGNN_HIP_TRY(ensure_dynamic_lds((const void*)linear_group_kernel<KSV, MV>, lds)); \
-        hipLaunchKernelGGL((linear_group_kernel<KSV, MV>), dim3((unsigned)grid), dim3(256), lds, s, p); } while (0)
-#define KP_LG(KSV) do { if (m == 1) KP_LG2(KSV, 1); else if (m == 2) KP_LG2(KSV, 2); else if (m == 3) KP_LG2(KSV, 3); \
-                        else if (m == 4) KP_LG2(KSV, 4); else KP_LG2(KSV, 6); } while (0)
-    switch (d->I) {
-        case 32: KP_LG(16); break;
-        case 64: KP_LG(32); break;
-        case 96: KP_LG(48); break;
-        case 104: KP_LG(52); break;
-        default: KP_LG(64); break;
-    }
-#undef KP_LG
-#undef KP_LG2
+    const int rc = LinWidths::dispatch(d->I, "linear_group_fwd", [&](auto KS) {
+        auto go = [&](auto M) {
+            KPGNN_HIP_TRY(ensure_dynamic_lds((const void*)linear_group_kernel<KS(), M()>, lds));
+            hipLaunchKernelGGL((linear_group_kernel<KS(), M()>), dim3(t.grid), dim3(256), lds, s, p);
+            return (int)KPGNN_OK;
+        };
+        switch (t.m) {
+            case 1: return go(std::integral_constant<int, 1>{});
+            case 2: return go(std::integral_constant<int, 2>{});
+            case 3: return go(std::integral_constant<int, 3>{});
+            case 4: return go(std::integral_constant<int, 4>{});
+            default: return go(std::integral_constant<int, 6>{});
+        }
+    });
+    if (rc != KPGNN_OK) return rc;
     KPGNN_LAUNCH_CHECK("linear_group_kernel");
     return KPGNN_OK;
 }

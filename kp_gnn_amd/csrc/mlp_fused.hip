@@ -9,8 +9,8 @@ extern "C" int kpgnn_linear_bn(const kpgnn_linear_bn_desc* d, kpgnn_stream_t str
     KPGNN_REQUIRE(d->x && d->w && d->y, "linear_bn: NULL pointer");
     KPGNN_REQUIRE(d->pro >= 0 && d->pro <= 3 && d->epi >= 0 && d->epi <= 2, "linear_bn: bad pro=%d / epi=%d", d->pro, d->epi);
     KPGNN_REQUIRE(d->pro < 2 || d->bias == nullptr, "linear_bn: the backward variants (pro %d) take no bias", d->pro);
-    if (!lin_supported_width(d->I) || (d->O % 4) != 0 || d->O > 128)
-        return fail(KPGNN_ELIMIT, "linear_bn: I=%d must be one of 32, 64, 96, 104, 128 and O=%d a multiple of 4 <= 128", d->I, d->O);
+    if (!LinWidths::has(d->I)) return LinWidths::refuse(d->I, "linear_bn");
+    if ((d->O % 4) != 0 || d->O > 128) return fail(KPGNN_ELIMIT, "linear_bn: O=%d must be a multiple of 4 <= 128", d->O);
     uintptr_t al = (uintptr_t)d->x | (uintptr_t)d->y | (uintptr_t)d->bias | (uintptr_t)d->x2 | (uintptr_t)d->xt | (uintptr_t)d->e_x;
     if (!d->w_transposed) al |= (uintptr_t)d->w;
     if (al & 15) return fail(KPGNN_ELIMIT, "linear_bn: operands must be 16-B aligned");
@@ -53,16 +53,7 @@ extern "C" int kpgnn_linear_bn(const kpgnn_linear_bn_desc* d, kpgnn_stream_t str
         }
         return linear3_fused(p, d->pro, d->epi, (const uint4*)d->workspace, s);
     }
-    switch (d->pro * 10 + d->epi) {
-        case 0: return lin_launch_plain(p, s);
-        case 1: return lin_launch_stats(p, s);
-        case 10: return lin_launch_bn(p, s);
-        case 11: return lin_launch_bn_stats(p, s);
-        case 20: return lin_launch_bwd(p, s);
-        case 22: return lin_launch_bwd_reduce(p, s);
-        case 32: return lin_launch_bwd2_reduce(p, s);
-        default: return fail(KPGNN_ELIMIT, "linear_bn: combination pro=%d epi=%d is not instantiated", d->pro, d->epi);
-    }
+    return dispatch_pro_epi(d->pro, d->epi, "linear_bn", [&](auto PRO, auto EPI) { return lin_fused_launch<PRO(), EPI()>(p, s); });
 }
 
 extern "C" size_t kpgnn_stat_slot_bytes(int32_t C) {

@@ -18,6 +18,7 @@
 // holds it) adds the slots of its followers in wave order.  Every sum therefore has one fixed order: results are
 // bitwise reproducible (the replay == eager test relies on it), and no float atomic is contended.
 // Per-block tables go to a workspace slab with plain stores; a second launch adds the slabs in block order.
+#include "bf3.h"
 #include "kpgnn_common.h"
 
 namespace kpgnn {
@@ -523,11 +524,9 @@ table_grad_kernel(TgParams p, int AS) {
 // Wave w computes hop w of the tile (g = theta[w] * gh[i] * gelu'(S[i,w]): written to global memory for the transposed gather
 // and, split, to LDS as MFMA B-operands); waves (mt, nt) = (w / 4, w % 4) own the 32 x 32 block of the 64 x 128 accumulator
 // table for the whole launch (16 registers), written to the slab once at the end.
-typedef __attribute__((ext_vector_type(8))) __bf16 tg_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float tg_f32x16;
 constexpr int kCntPitch = 72;      // bytes per code row of the count matrix: 64 rows + 8 (stride of 18 words: conflict-free 8-byte reads)
 
-__device__ __forceinline__ void tg_split3(const float (&x)[8], tg_bf16x8& hi, tg_bf16x8& mid, tg_bf16x8& lo) {
+__device__ __forceinline__ void tg_split3(const float (&x)[8], bf3_x8& hi, bf3_x8& mid, bf3_x8& lo) {
 #pragma unroll
     for (int n = 0; n < 8; ++n) {
         const __bf16 h = (__bf16)x[n];
@@ -634,7 +633,7 @@ tg_fuse_mfma_kernel(TgParams p) {
     int gbuf = 0;
     float th_a = 0.f, th_b = 0.f, gth_a = 0.f, gth_b = 0.f;
     if (fwave && col_ok) { th_a = p.theta[hop * D + c]; th_b = p.theta[hop * D + c + 1]; }
-    tg_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc[v] = 0.f;
     const int mt = w >> 2, nt = w & 3, li = lane & 31, kg = lane >> 5;
@@ -693,7 +692,7 @@ tg_fuse_mfma_kernel(TgParams p) {
                 }
             }
             if (col_ok) {                           // row block w as MFMA B operands (fp32: split three ways; bf16: exact as is)
-                tg_bf16x8 hi, mid, lo;
+                bf3_x8 hi, mid, lo;
                 tg_split3(ga, hi, mid, lo);
                 planes[(0 * 8 + w) * PC + c] = __builtin_bit_cast(uint4, hi);
                 if (!BF) {
@@ -720,19 +719,19 @@ tg_fuse_mfma_kernel(TgParams p) {
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const uint2 cw = *reinterpret_cast<const uint2*>(crow + 16 * ks);
-                tg_bf16x8 a;
+                bf3_x8 a;
                 a[0] = (__bf16)(float)(cw.x & 0xFFu); a[1] = (__bf16)(float)((cw.x >> 8) & 0xFFu);
                 a[2] = (__bf16)(float)((cw.x >> 16) & 0xFFu); a[3] = (__bf16)(float)(cw.x >> 24);
                 a[4] = (__bf16)(float)(cw.y & 0xFFu); a[5] = (__bf16)(float)((cw.y >> 8) & 0xFFu);
                 a[6] = (__bf16)(float)((cw.y >> 16) & 0xFFu); a[7] = (__bf16)(float)(cw.y >> 24);
                 const int rb = 2 * ks + kg;
                 if (!BF) {
-                    const tg_bf16x8 b2 = __builtin_bit_cast(tg_bf16x8, planes[(2 * 8 + rb) * PC + pc]);
-                    const tg_bf16x8 b1 = __builtin_bit_cast(tg_bf16x8, planes[(1 * 8 + rb) * PC + pc]);
+                    const bf3_x8 b2 = __builtin_bit_cast(bf3_x8, planes[(2 * 8 + rb) * PC + pc]);
+                    const bf3_x8 b1 = __builtin_bit_cast(bf3_x8, planes[(1 * 8 + rb) * PC + pc]);
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b2, acc, 0, 0, 0);     // smallest terms first
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b1, acc, 0, 0, 0);
                 }
-                const tg_bf16x8 b0 = __builtin_bit_cast(tg_bf16x8, planes[(0 * 8 + rb) * PC + pc]);
+                const bf3_x8 b0 = __builtin_bit_cast(bf3_x8, planes[(0 * 8 + rb) * PC + pc]);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b0, acc, 0, 0, 0);
             }
         }

@@ -13,7 +13,7 @@
 // Accumulators live in registers for the whole launch; per-block partials are added in block order (deterministic).
 #include <cstdlib>
 
-#include "kpgnn_common.h"
+#include "mfma_tile.h"
 
 namespace kpgnn {
 namespace {
@@ -243,7 +243,7 @@ bool tgm_plan(int N, int K, int D, int NT, int n0, int nk, int U, bool dsrc1, Tg
     if (pl->rows > 128 || D > 256) return false;
     pl->QS = (pl->rows + 3) / 4;
     const int cp = 4 * pl->QS;
-    pl->CP = cp + ((4 - cp % 8) + 8) % 8;             // pitch = 4 (mod 8): conflict-free 16 x 4 operand reads
+    pl->CP = mfma_pitch(cp);                          // conflict-free 16 x 4 operand reads
     pl->RE = n0 + nk;
     pl->REp = (pl->RE + 15) & ~15;
     pl->Rp = pl->REp + ((U + 15) & ~15);

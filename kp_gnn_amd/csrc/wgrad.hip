@@ -18,7 +18,6 @@
 namespace kpgnn {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 constexpr int kWgradBlocks = 512;
 
 struct WgParams {
@@ -779,172 +778,4 @@ extern "C" int kpgnn_linear_wgrad_group(const kpgnn_wgrad_desc* d, const float* 
         return KPGNN_OK;
     }
     return slab_reduce(A.slab, grid, nw + d->O, d->dw, nw, db, d->O, nullptr, s);
-}
-
-// ------------------------------------------------------------------------------------------------ y = x W^T + b
-namespace kpgnn {
-namespace {
-
-struct LinParams {
-    int64_t N; int O, I, pitch, ypitch, wt;
-    const float* x; int64_t xs;
-    const float* xmask; const int32_t* n_dyn;   // optional ReLU mask of x (same layout), optional live-row count
-    const float* w; const float* bias;
-    float* y; int64_t ys;
-    int yb; int64_t ybs;   // wide kernel: output column o lands in block o / yb at column o % yb; blocks are ybs floats apart (yb == O: plain rows)
-};
-
-// Wide outputs (O > 128, e.g. the input gradient of the jumping-knowledge projection: [N,104] x [104,936]): the x tile
-// stays resident in LDS while the block walks the outputs 128 at a time - per chunk every wave reloads its strip of the
-// weight (L2-resident) and runs its MFMA chains; results go straight from the accumulators to y (64 x 16-B segments per
-// store: measured as fast as staging through LDS), so no barrier separates the chunks.
-template <int KS, int M>
-__global__ void __launch_bounds__(256, 2)
-linear_wide_kernel(const LinParams p) {
-    extern __shared__ __attribute__((aligned(16))) float xl[];      // [32*M][pitch]
-    constexpr int ROWS = 32 * M;
-    constexpr int IC = 2 * KS;                        // == I (host)
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int kk = lane >> 5, c = lane & 31;
-    const int O = p.O, pitch = p.pitch;
-    const int64_t N = p.n_dyn ? (int64_t)min((int64_t)*p.n_dyn, p.N) : p.N;
-    const int64_t tiles = (N + ROWS - 1) / ROWS;
-    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        __syncthreads();                               // previous tile fully consumed
-        {   // x tile -> LDS (no register double-buffer: the eight output chunks dwarf this load)
-            const int64_t r0 = tile * ROWS;
-            const int lim = (int)(N - r0 < ROWS ? N - r0 : ROWS) * IC;
-            const float* base = p.x + r0 * p.xs;
-            for (int e = 4 * tid; e < ROWS * IC; e += 4 * 256) {
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (e < lim) {
-                    v = *reinterpret_cast<const float4*>(base + e);
-                    if (p.xmask) {
-                        const float4 mk = *reinterpret_cast<const float4*>(p.xmask + r0 * p.xs + e);
-                        if (mk.x <= 0.f) v.x = 0.f; if (mk.y <= 0.f) v.y = 0.f; if (mk.z <= 0.f) v.z = 0.f; if (mk.w <= 0.f) v.w = 0.f;
-                    }
-                }
-                *reinterpret_cast<float4*>(xl + (e / IC) * pitch + (e % IC)) = v;
-            }
-        }
-        __syncthreads();
-        const int64_t r0 = tile * ROWS;
-        const float* b0 = xl + c * pitch + kk;
-#pragma unroll 1
-        for (int chunk = (int)blockIdx.y * 128; chunk < O; chunk += 128 * (int)gridDim.y) {   // (few row tiles: chunks over blockIdx.y)
-            // the operand reads below do not depend on the chunk: without this the compiler hoists all of them out of
-            // the loop and spills ~500 registers
-            int z = 0;
-            asm volatile("" : "+v"(z));
-            const float* bz = b0 + z;
-            const int o = chunk + wave * 32 + c;
-            float a[KS];
-            if (p.wt) {
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) a[ks] = o < O ? p.w[(int64_t)(2 * ks + kk) * O + o] : 0.f;
-            } else {
-#pragma unroll
-                for (int j = 0; j < KS / 2; ++j) {
-                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (o < O) v = *reinterpret_cast<const float4*>(p.w + (int64_t)o * IC + 4 * j);
-                    a[2 * j] = kk ? v.y : v.x;
-                    a[2 * j + 1] = kk ? v.w : v.z;
-                }
-            }
-            f32x16 acc[M];
-#pragma unroll
-            for (int m = 0; m < M; ++m)
-                for (int v = 0; v < 16; ++v) acc[m][v] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-                for (int m = 0; m < M; ++m) {
-                    const float xv = bz[m * 32 * pitch + 2 * ks];
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ks], xv, acc[m], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int ob = chunk + wave * 32 + 8 * g + 4 * kk;
-                if (ob < O) {
-                    float4 bb = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (p.bias) bb = *reinterpret_cast<const float4*>(p.bias + ob);
-#pragma unroll
-                    for (int m = 0; m < M; ++m) {
-                        const int64_t r = r0 + m * 32 + c;
-                        if (r < N)
-                            *reinterpret_cast<float4*>(p.y + (int64_t)(ob / p.yb) * p.ybs + r * p.ys + (ob % p.yb)) =
-                                make_float4(acc[m][4 * g] + bb.x, acc[m][4 * g + 1] + bb.y, acc[m][4 * g + 2] + bb.z, acc[m][4 * g + 3] + bb.w);
-                    }
-                }
-            }
-        }
-    }
-}
-
-}  // namespace
-}  // namespace kpgnn
-
-extern "C" int kpgnn_linear_fwd(const kpgnn_linear_desc* d, kpgnn_stream_t stream) {
-    KPGNN_REQUIRE(d != nullptr, "linear_fwd: NULL descriptor");
-    KPGNN_REQUIRE(d->N >= 1 && d->O >= 1 && d->I >= 1, "linear_fwd: bad N=%lld O=%d I=%d", (long long)d->N, d->O, d->I);
-    if (d->O > 4096 || d->I > 128) return fail(KPGNN_ELIMIT, "linear_fwd: O=%d exceeds 4096 or I=%d exceeds 128", d->O, d->I);
-    KPGNN_REQUIRE(d->x && d->w && d->y, "linear_fwd: NULL pointer");
-    const bool blocked = d->y_block_cols > 0 && d->y_block_cols < d->O;   // output split into column blocks ([S, N, yb] layout)
-    if (blocked && ((d->y_block_cols % 4) != 0 || (d->O % d->y_block_cols) != 0 || d->y_stride != d->y_block_cols ||
-                    (d->y_block_stride % 4) != 0 || d->O <= 128))
-        return fail(KPGNN_ELIMIT, "linear_fwd: blocked output needs O > 128, O %% y_block_cols == 0, y_block_cols %% 4 == 0, "
-                                  "y_stride == y_block_cols and a 16-B aligned block stride");
-    if ((d->O % 4) != 0 || (d->I % 4) != 0 || d->x_stride != d->I || (!blocked && d->y_stride != d->O) ||
-        (((uintptr_t)d->x | (uintptr_t)d->y) & 15) != 0 || (d->bias && (((uintptr_t)d->bias) & 15) != 0))
-        return fail(KPGNN_ELIMIT, "linear_fwd: needs contiguous 16-B aligned x / y with I %% 4 == 0 and O %% 4 == 0");
-    hipStream_t s = (hipStream_t)stream;
-    if (d->O <= 128 && d->x_mask) return fail(KPGNN_ELIMIT, "linear_fwd: x_mask is implemented for O > 128");
-    if (d->x_mask && (((uintptr_t)d->x_mask) & 15) != 0) return fail(KPGNN_ELIMIT, "linear_fwd: x_mask must be 16-B aligned");
-    if (d->O <= 128) {                                  // the plain variant of the fused kernel (lin_fused.h)
-        kpgnn_linear_bn_desc f = {};
-        f.N = d->N; f.n_dyn = d->n_dyn; f.O = d->O; f.I = d->I; f.x = d->x; f.w = d->w; f.bias = d->bias; f.y = d->y; f.w_transposed = d->w_transposed;
-        return kpgnn_linear_bn(&f, stream);
-    }
-    if (blocked && (((uintptr_t)d->w) & 15) == 0) {
-        bool handled = false;
-        const int rc = linear3_blocked(d, s, &handled);                            // the bf16-split kernel, where it applies
-        if (handled || rc != KPGNN_OK) return rc;
-    }
-    if (d->I != 32 && d->I != 64 && d->I != 104 && d->I != 128)
-        return fail(KPGNN_ELIMIT, "linear_fwd: wide outputs need I in {32, 64, 104, 128} (the k-loop is fully unrolled)");
-    LinParams p;
-    p.N = d->N; p.O = d->O; p.I = d->I; p.wt = d->w_transposed ? 1 : 0;
-    const int rowp = d->I + ((4 - d->I % 8) + 8) % 8;   // pitch = 4 (mod 8) floats: 16-B aligned rows, conflict-free 16-B accesses
-    p.pitch = rowp; p.ypitch = rowp;
-    p.x = d->x; p.xs = d->x_stride; p.w = d->w; p.bias = d->bias; p.y = d->y; p.ys = d->y_stride;
-    p.xmask = d->x_mask; p.n_dyn = d->n_dyn;
-    p.yb = blocked ? d->y_block_cols : d->O; p.ybs = blocked ? d->y_block_stride : 0;
-    // rows per tile = 32 * m, m in 1..3, the smallest that makes the launch one round over two blocks per CU
-    const int64_t slots = (int64_t)device_facts().cu_count * 2;
-    int m = (int)((d->N + slots * 32 - 1) / (slots * 32));
-    m = m < 1 ? 1 : (m > 3 ? 3 : m);
-    const int rows = 32 * m;
-    const size_t lds = sizeof(float) * (size_t)rows * rowp;
-    const int64_t tiles = (d->N + rows - 1) / rows;
-    const int64_t grid = (m == 1 ? slots * 2 : slots) < tiles ? (m == 1 ? slots * 2 : slots) : tiles;
-    dim3 blk(256);
-    const int ks = (d->I + 1) / 2;
-    // a small batch has fewer row tiles than the chip has block slots: the output chunks of a tile are then spread over
-    // blockIdx.y instead of walked one after the other (batch 64, [1.5k,104] x [104,936]: one block chain of 8 chunks, 31 us)
-    const int64_t nchunks = (d->O + 127) / 128;
-    int64_t gy = tiles < slots ? (slots + tiles - 1) / tiles : 1;
-    if (gy > nchunks) gy = nchunks;
-#define KP_LIN2(KSV, MV) do { \
-        KPGNN_HIP_TRY(ensure_dynamic_lds((const void*)linear_wide_kernel<KSV, MV>, lds)); \
-        hipLaunchKernelGGL((linear_wide_kernel<KSV, MV>), dim3((unsigned)grid, (unsigned)gy), blk, lds, s, p); } while (0)
-#define KP_LIN(KSV) do { if (m == 1) KP_LIN2(KSV, 1); else if (m == 2) KP_LIN2(KSV, 2); else KP_LIN2(KSV, 3); } while (0)
-    if (ks == 16) KP_LIN(16);
-    else if (ks == 32) KP_LIN(32);
-    else if (ks == 52) KP_LIN(52);
-    else KP_LIN(64);
-#undef KP_LIN
-#undef KP_LIN2
-    KPGNN_LAUNCH_CHECK("linear_wide_kernel");
-    return KPGNN_OK;
 }

@@ -141,7 +141,7 @@ def set_dense_math(mode):
     _lib.DENSE_MATH = {"auto": _lib.MATH_AUTO, "f32": _lib.MATH_F32}[mode]
 
 
-_LIN_WIDTHS = (32, 64, 96, 104, 128)   # lin_fused.h: fully unrolled k-loops
+_LIN_WIDTHS = (32, 64, 96, 104, 128)   # mfma_tile.h LinWidths: fully unrolled k-loops
 
 # kpgnn_linear_fwd: y = x W^T + b and dx = dy W for tall-skinny x on the fp32 matrix cores.  Measured 21.8 us per
 # [47k,104] x [104,104] launch against 29 us for the BLAS library's kernel (profiles/r01): on by default for the shapes
@@ -153,7 +153,6 @@ _LIN_WIDTHS = (32, 64, 96, 104, 128)   # lin_fused.h: fully unrolled k-loops
 def _mfma_linear(x, w, bias, transposed=False):
     """y = x w^T + bias on kpgnn_linear_fwd (w: [O,I] contiguous), or y = x w with transposed=True (w: [I,O]).
     Returns None when the shape is not covered."""
-    lib = _lib.load()
     N, I = x.shape
     O = w.shape[1] if transposed else w.shape[0]
     if (O % 4 != 0 or I not in _LIN_WIDTHS or (O > 128 and I == 96) or O > 4096 or N < 1024 or not x.is_contiguous()
@@ -165,11 +164,8 @@ def _mfma_linear(x, w, bias, transposed=False):
     d.n_dyn = dyn_ptr(N)
     d.w_transposed = 1 if transposed else 0
     d.x, d.x_stride, d.w, d.bias, d.y, d.y_stride = x.data_ptr(), x.stride(0), w.data_ptr(), _ptr(bias), y.data_ptr(), y.stride(0)
-    with torch.cuda.device(x.device):
-        rc = lib.kpgnn_linear_fwd(ctypes.byref(d), torch.cuda.current_stream(x.device).cuda_stream)
-    if rc == -3:
+    if _lib.launch("kpgnn_linear_fwd", x.device, ctypes.byref(d), allow=(_lib.ELIMIT,)) == _lib.ELIMIT:
         return None
-    _lib.check(rc, "kpgnn_linear_fwd")
     return y
 
 

@@ -52,6 +52,29 @@ def test_argument_validation_without_gpu(built):
     assert lib.kpgnn_csr_stats(None, 0, None, 0, 5, 2, None, None) == -1
 
 
+def test_linear_bn_refuses_a_pair_that_is_not_instantiated_without_gpu(built):
+    """An otherwise valid kpgnn_linear_bn descriptor with (pro, epi) = (1, 2): the one table of instantiated pairs answers
+    KPGNN_ELIMIT before any device call, with the same text on the fp32 route and on the bf16-split route (N >= 4096, a
+    workspace of sufficient size whose split copy of W is declared ready)."""
+    from kp_gnn_amd import _lib
+    lib = _lib.load()
+    a = 0x10000                                       # dummy, non-NULL, 16-B aligned: never dereferenced
+    d = _lib.LinearBnDesc()
+    d.N, d.O, d.I, d.pro, d.epi = 1000, 32, 32, 1, 2
+    for f in ("x", "w", "y", "in_slot", "in_gamma", "in_beta", "in_mean", "in_invstd", "out_slot",
+              "e_x", "e_mean", "e_invstd", "e_gamma", "e_beta"):
+        setattr(d, f, a)
+    d.math = _lib.MATH_F32
+    assert lib.kpgnn_linear_bn(ctypes.byref(d), None) == -3
+    text = lib.kpgnn_last_error()
+    assert b"combination pro=1 epi=2 is not instantiated" in text
+    d.N, d.math = 4096, _lib.MATH_AUTO
+    d.workspace, d.workspace_bytes, d.w_split_ready = a, lib.kpgnn_linear_split_workspace_bytes(32, 32, 1), 1
+    assert d.workspace_bytes > 0
+    assert lib.kpgnn_linear_bn(ctypes.byref(d), None) == -3
+    assert lib.kpgnn_last_error() == text
+
+
 def test_product_refuses_cpu_tensors(built):
     import torch
     from kp_gnn_amd import KpgnnError

@@ -1346,6 +1346,26 @@ def _gpu_relu_masks(node):
                                    (4096, 128, 128)])
 @pytest.mark.parametrize("follow_norm", [False, True, "fused", "fused_cell"])
 def test_fused_mlp_vs_torch(N, I, O, follow_norm):
+    _fused_mlp_case(N, I, O, follow_norm)
+
+
+# lin_fused_kernel's tile height is m = ceil(N / (2 * CUs * 32)), capped at 3; with 256 CUs m = 2 starts at N = 16385 and m = 3
+# at N = 32769, and under "auto" every N >= 4096 with I <= 104 belongs to the bf16-split kernels: only "f32" reaches m = 2, 3.
+@pytest.mark.parametrize("N,I,O", [(4099, 104, 104),      # m = 1, a ragged last tile
+                                   (16500, 64, 104),      # m = 2
+                                   (33000, 104, 104)])    # m = 3
+@pytest.mark.parametrize("follow_norm", [False, True, "fused", "fused_cell"])
+def test_fused_mlp_vs_torch_f32(N, I, O, follow_norm):
+    """The same comparison, same tolerances, with the fp32 matrix instruction everywhere (set_dense_math("f32"))."""
+    from kp_gnn_amd import ops_dense
+    ops_dense.set_dense_math("f32")
+    try:
+        _fused_mlp_case(N, I, O, follow_norm)
+    finally:
+        ops_dense.set_dense_math("auto")
+
+
+def _fused_mlp_case(N, I, O, follow_norm):
     """kpgnn_linear_bn + slots: Linear-BN-ReLU-Linear-BN-ReLU (KPGINplus.py:25-30) in 3 + 5 launches against the same
     sequence of torch ops on the CPU in FLOAT64 (training mode; an fp32 CPU batch_norm is itself 4e-4 .. 8e-3 of the gradient
     scale away from float64 at 4096 x 128 x 128, depending on its thread count): output, running statistics, the input gradient
