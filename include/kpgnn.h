@@ -753,6 +753,52 @@ typedef struct kpgnn_linear_bn_desc {
 int kpgnn_linear_bn(const kpgnn_linear_bn_desc* d, kpgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Evaluation mode (model.eval() under torch.no_grad(): the reference's val() / test() loops, train_ZINC.py:50-52,
+ * train_qm9.py:103-105, train_graph_property.py:52-54).  With running statistics a BatchNorm1d is a per-column map
+ *   bn(v) = (v - running_mean) * rsqrt(running_var + eps) * gamma + beta
+ * so no grid-wide reduction sits between the two Linears of the layers' MLP.  The running statistics (and the module's
+ * num_batches_tracked, which is not even passed) are only READ.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct kpgnn_bn_running {
+    const float* gamma; const float* beta;                  /* device [C] */
+    const float* running_mean; const float* running_var;    /* device [C] */
+    float eps;
+} kpgnn_bn_running;
+
+/* y = [outer(] relu(bn2(relu(bn1(x W0^T + b0)) W3^T + b3)) [)] [+ residual] in ONE launch (csrc/mlp_eval.hip): the
+ * Linear-BatchNorm-ReLU x2 MLP of KPGINPlusConv / GINEConv (KPGINplus.py:25-30, gine.py:31-38), the body's per-layer norm
+ * (models/GNNs.py:440-441) and its residual add.  x is read once, y written once; relu(bn1(.)) lives in LDS only.  Each
+ * norm is applied after the bias, in the order above (the scale is NOT folded into the weights); the kernel forms the
+ * per-column coefficients in its prologue.  I and O in {32, 64, 96, 104, 128}, row strides multiples of 4, 16-B aligned
+ * operands: KPGNN_ELIMIT otherwise.  The outer norm is absent when outer.gamma is NULL. */
+typedef struct kpgnn_mlp_eval_desc {
+    int64_t N;
+    int32_t I, O;
+    const float* x; int64_t x_stride;       /* device [N,I], row stride in elements */
+    const float* w0; const float* b0;       /* device [O,I] contiguous; [O] or NULL */
+    const float* w3; const float* b3;       /* device [O,O] contiguous; [O] or NULL */
+    kpgnn_bn_running bn1, bn2, outer;
+    const float* residual; int64_t r_stride;/* optional device [N,O] */
+    float* y; int64_t y_stride;             /* device [N,O] */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= N; kpgnn_wgrad_desc explains); NULL: all N rows */
+    int32_t math;               /* KPGNN_MATH_*; both settings run the fp32 matrix instruction (there is no bf16-split route) */
+} kpgnn_mlp_eval_desc;
+int kpgnn_mlp_eval(const kpgnn_mlp_eval_desc* d, kpgnn_stream_t stream);
+
+/* z = [relu](bn(x)) [+ residual] over [N, C] rows with running statistics, C <= 256 (csrc/bn_eval.hip): the bodies'
+ * per-layer norm of GNN / GNNPrime and the MLP norms of widths kpgnn_mlp_eval does not take.  One streaming launch. */
+typedef struct kpgnn_bn_eval_desc {
+    int64_t N;
+    int32_t C, relu;
+    const float* x; int64_t x_stride;       /* device [N,C], row stride in elements */
+    kpgnn_bn_running bn;
+    const float* residual; int64_t r_stride;/* optional: z += residual (after the activation) */
+    float* z; int64_t z_stride;             /* device [N,C] output */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= N; kpgnn_wgrad_desc explains); NULL: all N rows */
+} kpgnn_bn_eval_desc;
+int kpgnn_bn_eval(const kpgnn_bn_eval_desc* d, kpgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Graph readout over a collated batch (models/GraphRegression.py:46-51: PyG global_add_pool / global_mean_pool):
  *   out[g,:] = sum (mode 0) or mean (mode 1) of x[n,:] over the nodes n of graph g;  gx[n,:] = gout[batch[n],:] (/ count)
  * The nodes of a graph are contiguous (graph_ptr[g] .. graph_ptr[g+1]), rows are added in node order: bitwise

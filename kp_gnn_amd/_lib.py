@@ -220,6 +220,33 @@ class LinearGroupDesc(ctypes.Structure):
         self.math = DENSE_MATH
 
 
+class BnRunning(ctypes.Structure):
+    _fields_ = [("gamma", c_vp), ("beta", c_vp), ("running_mean", c_vp), ("running_var", c_vp), ("eps", ctypes.c_float)]
+
+
+class MlpEvalDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("I", c_i32), ("O", c_i32),
+        ("x", c_vp), ("x_stride", c_i64), ("w0", c_vp), ("b0", c_vp), ("w3", c_vp), ("b3", c_vp),
+        ("bn1", BnRunning), ("bn2", BnRunning), ("outer", BnRunning),
+        ("residual", c_vp), ("r_stride", c_i64), ("y", c_vp), ("y_stride", c_i64),
+        ("n_dyn", c_vp), ("math", c_i32),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.math = DENSE_MATH
+
+
+class BnEvalDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("C", c_i32), ("relu", c_i32),
+        ("x", c_vp), ("x_stride", c_i64), ("bn", BnRunning),
+        ("residual", c_vp), ("r_stride", c_i64), ("z", c_vp), ("z_stride", c_i64),
+        ("n_dyn", c_vp),
+    ]
+
+
 class HopMlpDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i64), ("K", c_i32), ("DI", c_i32), ("DO", c_i32), ("H", c_i32),
@@ -327,6 +354,8 @@ SIGNATURES = {
     "kpgnn_wgrad_group_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "kpgnn_linear_wgrad_group": (ctypes.c_int, [ctypes.POINTER(WgradDesc), c_vp, c_i32, c_vp]),
     "kpgnn_linear_bn": (ctypes.c_int, [ctypes.POINTER(LinearBnDesc), c_vp]),
+    "kpgnn_mlp_eval": (ctypes.c_int, [ctypes.POINTER(MlpEvalDesc), c_vp]),
+    "kpgnn_bn_eval": (ctypes.c_int, [ctypes.POINTER(BnEvalDesc), c_vp]),
     "kpgnn_enc_tables_fwd": (ctypes.c_int, [ctypes.POINTER(EncTablesDesc), c_vp]),
     "kpgnn_enc_tables_bwd": (ctypes.c_int, [ctypes.POINTER(EncTablesDesc), c_vp]),
     "kpgnn_segment_pool_fwd": (ctypes.c_int, [ctypes.POINTER(PoolDesc), c_vp]),

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from .layers.gine import GINEConv
 from .ops import DictPeripheral, embedding_rows, enc_tables, segment_pool, table_gather_sum
-from .ops_dense import JKConcatLinear, batch_norm_act, prepare_mlp_splits, score_head
+from .ops_dense import JKConcatLinear, batch_norm_act, jk_concat_linear_nograd, prepare_mlp_splits, score_head
 
 MAX_DICT_ROWS = 128  # peripheral dictionaries up to this many distinct tuples use the dictionary kernels
 
@@ -371,6 +371,12 @@ class _KHopBody(nn.Module):
         if self.JK == "concat" and h_list[0].is_cuda and h_list[0].dtype == torch.float32 and torch.is_grad_enabled():
             lin = self.output_proj[0]
             return self.output_proj[2](JKConcatLinear.apply(lin.weight, lin.bias, *h_list))
+        if self.JK == "concat" and h_list[0].is_cuda and h_list[0].dtype == torch.float32:
+            # no grad (evaluation): the grouped-K kernel directly - no autograd node, nothing saved
+            lin = self.output_proj[0]
+            y = jk_concat_linear_nograd(lin.weight, lin.bias, h_list)
+            if y is not None:
+                return self.output_proj[2](y)
         if self.JK == "concat":
             rep = torch.cat(h_list, dim=1)
         elif self.JK == "last":

@@ -1,7 +1,8 @@
 """Dense tail of the layers: training-mode BatchNorm1d (+ReLU, +residual) on the HIP kernels of bn.hip.
 
 The nn.BatchNorm1d modules stay where the reference has them (state_dict keys `mlp.1.*`, `norms.l.module.*`);
-only their training-mode arithmetic is routed here.  Eval mode (running statistics) uses torch's own GPU op."""
+their training-mode arithmetic is routed here, and so is evaluation mode under torch.no_grad() (running statistics:
+kpgnn_mlp_eval / kpgnn_bn_eval).  Eval mode with grad enabled uses torch's own GPU op."""
 import ctypes
 
 import torch
@@ -223,7 +224,13 @@ def linear(x, lin):
 
 def batch_norm_act(x, bn, relu=False, residual=None):
     """nn.BatchNorm1d `bn` applied to x [N,C] (+ReLU) (+residual).  Training mode with batch statistics runs
-    on the HIP kernels; everything else (eval, no affine, cumulative momentum, C > 256) on torch's GPU op."""
+    on the HIP kernels, and so does eval mode with running statistics under torch.no_grad() (kpgnn_bn_eval); everything
+    else (eval with grad enabled, no affine, cumulative momentum, C > 256) on torch's GPU op."""
+    if (not torch.is_grad_enabled() and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] >= 1
+            and x.shape[1] <= 256 and _eval_bn(bn) and _eval_residual_ok(residual, x.shape)):
+        z = bn_eval_raw(x, bn, relu=relu, residual=residual)
+        if z is not None:
+            return z
     use_hip = (bn.training and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and bn.affine
                and bn.momentum is not None and x.shape[1] <= 256 and x.shape[0] >= 1)
     if use_hip:
@@ -238,6 +245,88 @@ def batch_norm_act(x, bn, relu=False, residual=None):
     if residual is not None:
         out = out + residual
     return out
+
+
+# ------------------------------------------------------------------------------------------- evaluation mode (no grad)
+def _eval_bn(bn):
+    """A BatchNorm1d the evaluation kernels take: eval mode, affine, fp32 running statistics on the device."""
+    return (not bn.training and bn.affine and bn.running_mean is not None and bn.running_var is not None
+            and bn.weight.is_cuda and bn.weight.dtype == torch.float32 and bn.running_mean.dtype == torch.float32)
+
+
+def _eval_residual_ok(res, shape):
+    return res is None or (res.is_cuda and res.dtype == torch.float32 and tuple(res.shape) == tuple(shape))
+
+
+def _set_running(r, bn):
+    r.gamma, r.beta, r.eps = bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps)
+    r.running_mean, r.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+
+
+def _eval_out(out, N, C, dev):
+    if out is None:
+        return torch.empty((N, C), dtype=torch.float32, device=dev)
+    assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (N, C) and out.stride(1) == 1
+    return out
+
+
+def bn_eval_raw(x, bn, relu=False, residual=None, out=None):
+    """[relu](bn(x)) [+ residual] with bn's running statistics as one kpgnn_bn_eval launch, into `out` when given (a
+    preallocated [N,C] fp32 tensor).  No autograd node; bn is only read.  None when the kernel does not take the shape."""
+    x = x if x.stride(-1) == 1 else x.contiguous()
+    N, C = x.shape
+    z = _eval_out(out, N, C, x.device)
+    d = _lib.BnEvalDesc()
+    d.N, d.C, d.relu = N, C, 1 if relu else 0
+    d.n_dyn = dyn_ptr(N)
+    d.x, d.x_stride, d.z, d.z_stride = x.data_ptr(), x.stride(0), z.data_ptr(), z.stride(0)
+    _set_running(d.bn, bn)
+    if residual is not None:
+        residual = residual if residual.stride(-1) == 1 else residual.contiguous()
+        d.residual, d.r_stride = residual.data_ptr(), residual.stride(0)
+    if _lib.launch("kpgnn_bn_eval", x.device, ctypes.byref(d), allow=(_lib.ELIMIT,)) == _lib.ELIMIT:
+        return None
+    return z
+
+
+def mlp_eval_raw(mlp, h, post_norm=None, out=None):
+    """[bnO(] relu(bn2(relu(bn1(h W0^T + b0)) W3^T + b3)) [)] [+ residual] on the modules' running statistics as ONE
+    kpgnn_mlp_eval launch, into `out` when given (a preallocated [N,O] fp32 tensor).  No autograd node; the modules are only
+    read.  post_norm = (nn.BatchNorm1d, residual or None).  None when the kernel does not take the shape (KPGNN_ELIMIT)."""
+    l0, bn1, l3, bn2 = mlp[0], mlp[1], mlp[3], mlp[4]
+    O, I = l0.weight.shape
+    bnO, res = post_norm if post_norm is not None else (None, None)
+    if I not in _LIN_WIDTHS or O not in _LIN_WIDTHS:
+        return None
+    h = h if h.stride(-1) == 1 else h.contiguous()
+    N = h.shape[0]
+    y = _eval_out(out, N, O, h.device)
+    w0, w3 = l0.weight.contiguous(), l3.weight.contiguous()
+    d = _lib.MlpEvalDesc()
+    d.N, d.I, d.O = N, I, O
+    d.n_dyn = dyn_ptr(N)
+    d.x, d.x_stride, d.y, d.y_stride = h.data_ptr(), h.stride(0), y.data_ptr(), y.stride(0)
+    d.w0, d.b0, d.w3, d.b3 = w0.data_ptr(), _ptr(l0.bias), w3.data_ptr(), _ptr(l3.bias)
+    _set_running(d.bn1, bn1)
+    _set_running(d.bn2, bn2)
+    if bnO is not None:
+        _set_running(d.outer, bnO)
+    if res is not None:
+        res = res if res.stride(-1) == 1 else res.contiguous()
+        d.residual, d.r_stride = res.data_ptr(), res.stride(0)
+    if _lib.launch("kpgnn_mlp_eval", h.device, ctypes.byref(d), allow=(_lib.ELIMIT,)) == _lib.ELIMIT:
+        return None
+    return y
+
+
+def _eval_linear(x, lin):
+    """nn.Linear under no_grad: kpgnn_linear_fwd where it takes the shape (N >= 1024, a covered width), else the module."""
+    if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and lin.weight.dtype == torch.float32:
+        y = _mfma_linear(x if x.is_contiguous() else x.contiguous(), lin.weight.contiguous(), lin.bias)
+        if y is not None:
+            return y
+    refuse_dynamic_rows("nn.Linear on the framework path", x.shape[0])
+    return lin(x)
 
 
 # Split copies of the MLPs' weights for the bf16-split Linear kernels (kpgnn_linear_split_many): a body prepares ALL of them,
@@ -463,6 +552,17 @@ def mlp_linear_bn_relu_x2(mlp, h, emit_out_stats=False, post_norm=None):
     l0, bn1, l3, bn2 = mlp[0], mlp[1], mlp[3], mlp[4]
     O, I = l0.weight.shape
     bnO, res = post_norm if post_norm is not None else (None, None)
+    if (not torch.is_grad_enabled() and h.is_cuda and h.dim() == 2 and h.dtype == torch.float32 and h.shape[0] >= 1
+            and _eval_bn(bn1) and _eval_bn(bn2) and (bnO is None or _eval_bn(bnO)) and tuple(l3.weight.shape) == (O, O)
+            and _eval_residual_ok(res, (h.shape[0], O))):
+        # evaluation: one launch for the MLP, the caller's norm and the residual; for a shape it does not take, the Linears on
+        # kpgnn_linear_fwd where that applies and the norms on kpgnn_bn_eval
+        z = mlp_eval_raw(mlp, h, post_norm=post_norm)
+        if z is not None:
+            return z
+        z = batch_norm_act(_eval_linear(h, l0), bn1, relu=True)
+        z = batch_norm_act(_eval_linear(z, l3), bn2, relu=True)
+        return z if bnO is None else batch_norm_act(z, bnO, relu=False, residual=res)
     if (h.is_cuda and h.dim() == 2 and h.dtype == torch.float32 and torch.is_grad_enabled() and _fusable_bn(bn1)
             and _fusable_bn(bn2) and I in _LIN_WIDTHS and O in _LIN_WIDTHS and tuple(l3.weight.shape) == (O, O)
             and h.shape[0] >= 1 and h.data_ptr() % 16 == 0
@@ -484,13 +584,14 @@ def mlp_linear_bn_relu_x2(mlp, h, emit_out_stats=False, post_norm=None):
 
 
 # ------------------------------------------------------------------------------------ jumping-knowledge projection
-def _jk_native_ok(weight, bias, states):
+def _jk_native_ok(weight, bias, states, forward_only=False):
     """Shapes the grouped-K kernels take: S <= 16 contiguous fp32 [N,H] states of one width H in {32, 64, 96, 104, 128},
-    O <= 128 with O % 4 == 0, S * H > 128 (the blocked input-gradient kernel), 16-B aligned operands."""
+    O <= 128 with O % 4 == 0, S * H > 128 (the blocked input-gradient kernel; not asked of a forward without grad), 16-B
+    aligned operands."""
     S = len(states)
     N, H = states[0].shape
     O = weight.shape[0]
-    return (2 <= S <= 16 and H in _LIN_WIDTHS and O % 4 == 0 and O in (32, 64, 104, 128) and S * H > 128 and N >= 1
+    return (2 <= S <= 16 and H in _LIN_WIDTHS and O % 4 == 0 and O in (32, 64, 104, 128) and (forward_only or S * H > 128) and N >= 1
             and tuple(weight.shape) == (O, S * H) and weight.is_contiguous() and weight.data_ptr() % 16 == 0
             and (bias is None or (bias.is_contiguous() and bias.data_ptr() % 16 == 0))
             and all(st.shape == (N, H) and st.dtype == torch.float32 and st.is_contiguous() and st.data_ptr() % 16 == 0 for st in states))
@@ -501,6 +602,33 @@ def _split_workspace(lib, O, I, group, device):
     order, rebuilt by every call (the weights change every step); None when the kernels do not take the shape."""
     nb = int(lib.kpgnn_linear_split_workspace_bytes(O, I, group))
     return torch.empty(nb, dtype=torch.uint8, device=device) if nb > 0 else None
+
+
+def _jk_group_fwd(weight, bias, states):
+    """relu(sum_l states[l] W[:, l*H:(l+1)*H]^T + b) by kpgnn_linear_group_fwd, for shapes _jk_native_ok accepts."""
+    lib = _lib.load()
+    N, H = states[0].shape
+    O = weight.shape[0]
+    y = torch.empty((N, O), dtype=torch.float32, device=weight.device)
+    d = _lib.LinearGroupDesc()
+    d.N, d.O, d.I, d.group = N, O, H, len(states)
+    d.n_dyn = dyn_ptr(N)
+    for l, st in enumerate(states):
+        d.x[l] = st.data_ptr()
+    d.x_stride, d.w, d.bias, d.y, d.relu = H, weight.data_ptr(), _ptr(bias), y.data_ptr(), 1
+    ws = _split_workspace(lib, O, H, len(states), weight.device)     # (the bf16-split kernel's copy of W; None: fp32 kernel)
+    if ws is not None:
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    _lib.launch("kpgnn_linear_group_fwd", weight.device, ctypes.byref(d))
+    return y
+
+
+def jk_concat_linear_nograd(weight, bias, states):
+    """The jumping-knowledge projection relu(cat(states, 1) W^T + b) under torch.no_grad(): kpgnn_linear_group_fwd directly -
+    no autograd node, nothing saved, no concatenated copy.  None for shapes the grouped-K kernel does not take."""
+    if not _jk_native_ok(weight, bias, states, forward_only=True):
+        return None
+    return _jk_group_fwd(weight, bias, states)
 
 
 class JKConcatLinear(torch.autograd.Function):
@@ -521,20 +649,7 @@ class JKConcatLinear(torch.autograd.Function):
         ctx.widths = [st.shape[1] for st in states]
         ctx.has_bias = bias is not None
         if ctx.native:
-            lib = _lib.load()
-            N, H = states[0].shape
-            O = weight.shape[0]
-            y = torch.empty((N, O), dtype=torch.float32, device=weight.device)
-            d = _lib.LinearGroupDesc()
-            d.N, d.O, d.I, d.group = N, O, H, len(states)
-            d.n_dyn = dyn_ptr(N)
-            for l, st in enumerate(states):
-                d.x[l] = st.data_ptr()
-            d.x_stride, d.w, d.bias, d.y, d.relu = H, weight.data_ptr(), _ptr(bias), y.data_ptr(), 1
-            ws = _split_workspace(lib, O, H, len(states), weight.device)     # (the bf16-split kernel's copy of W; None: fp32 kernel)
-            if ws is not None:
-                d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-            _lib.launch("kpgnn_linear_group_fwd", weight.device, ctypes.byref(d))
+            y = _jk_group_fwd(weight, bias, states)
             ctx.save_for_backward(weight, y, *states)
             return y
         refuse_dynamic_rows("the jumping-knowledge projection outside the grouped-K kernels' shapes", states[0].shape[0])
