@@ -820,6 +820,91 @@ int kpgnn_segment_pool_fwd(const kpgnn_pool_desc* d, kpgnn_stream_t stream);
 int kpgnn_segment_pool_bwd(const kpgnn_pool_desc* d, kpgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Attention readout (csrc/attn_pool.hip): PyG's AttentionalAggregation(gate_nn = nn.Linear(D, 1)) over the contiguous node
+ * ranges of graph_ptr (models/GraphClassification.py:31-32, models/GraphRegression.py "attention"):
+ *   gate[n] = x[n] . w + bias[0]      alpha[n] = exp(gate[n] - max_g) / (sum_{m in g} exp(gate[m] - max_g) + 1e-16)
+ *   out[g,:] = sum_{n in g} alpha[n] x[n,:]          (an empty graph gives a zero row)
+ * Forward: one launch, x read once; alpha [N] is kept for the backward.  Backward (s_g = gout[g] . out[g]):
+ *   dgate[n] = alpha[n] (gout[g] . x[n] - s_g)   gx[n,:] = alpha[n] gout[g,:] + dgate[n] w   dw = sum_n dgate[n] x[n,:]
+ *   db = sum_n dgate[n]
+ * in one launch plus one fixed-order reduce of the per-block partial sums (none when one block covers the batch).  Rows are
+ * added in node order, blocks in block order: bitwise reproducible.  D <= 256 (KPGNN_ELIMIT beyond).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct kpgnn_attn_pool_desc {
+    int64_t N;                  /* nodes */
+    int32_t G, D;               /* graphs, feature width */
+    const int32_t* graph_ptr;   /* device [G+1], non-decreasing, graph_ptr[G] == the live node count */
+    const float* x; int64_t x_stride;      /* device [N,D] */
+    const float* w;             /* device [D]: gate_nn.weight (the caller checks that it has D entries) */
+    const float* bias;          /* device [1]: gate_nn.bias, or NULL (forward only) */
+    float* alpha;               /* device [N]: written by the forward, read by the backward */
+    float* out;                 /* device [G,D] contiguous: written by the forward, read by the backward */
+    const float* gout;          /* device [G,D] contiguous (backward) */
+    float* gx; int64_t gx_stride;          /* device [N,D] (backward, overwritten; NULL: skipped) */
+    float* dw;                  /* device [D] (backward, overwritten) */
+    float* db;                  /* device [1] (backward, overwritten; NULL: skipped) */
+    void* workspace; size_t workspace_bytes;   /* backward: kpgnn_attn_pool_workspace_bytes(G, D) */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= N; kpgnn_wgrad_desc explains); NULL: all N rows */
+} kpgnn_attn_pool_desc;
+
+size_t kpgnn_attn_pool_workspace_bytes(int32_t G, int32_t D);
+int kpgnn_attn_pool_fwd(const kpgnn_attn_pool_desc* d, kpgnn_stream_t stream);
+int kpgnn_attn_pool_bwd(const kpgnn_attn_pool_desc* d, kpgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * nn.Linear with a narrow output (csrc/head_linear.hip): the classifiers and node-level regressors of
+ * models/GraphClassification.py:37, NodeClassification.py:21-24 and NodeRegression.py:18.
+ *   y[M,O] = x[M,I] W^T + bias          dx = dy W      dw = dy^T x      db = sum_m dy[m,:]
+ * 1 <= O <= 32 and I <= 1024 (O < 1 or I < 1: KPGNN_EINVAL; O > 32 or I > 1024: KPGNN_ELIMIT); M is any row count, 0 included.
+ * I is the width of x AND of w: a caller holding an nn.Linear checks in_features against x before the call.  Forward: one launch.  Backward: one launch in
+ * which every block covers a tile of rows and leaves a partial [O, I] (+ [O]) slab, plus one fixed-order reduce of the slabs
+ * (none when one block covers all rows): bitwise reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct kpgnn_head_linear_desc {
+    int64_t M;                  /* rows */
+    int32_t O, I;               /* out_features, in_features */
+    const float* x; int64_t x_stride;      /* device [M,I] */
+    const float* w;             /* device [O,I] contiguous */
+    const float* bias;          /* device [O] or NULL (forward) */
+    float* y; int64_t y_stride;            /* device [M,O] (forward) */
+    const float* dy; int64_t dy_stride;    /* device [M,O] (backward) */
+    float* dx; int64_t dx_stride;          /* device [M,I] (backward, overwritten; NULL: skipped) */
+    float* dw;                  /* device [O,I] contiguous (backward, overwritten) */
+    float* db;                  /* device [O] (backward, overwritten; NULL: skipped) */
+    void* workspace; size_t workspace_bytes;   /* backward: kpgnn_head_linear_workspace_bytes(M, O, I) */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= M; kpgnn_wgrad_desc explains); NULL: all M rows */
+} kpgnn_head_linear_desc;
+
+size_t kpgnn_head_linear_workspace_bytes(int64_t M, int32_t O, int32_t I);
+int kpgnn_head_linear_fwd(const kpgnn_head_linear_desc* d, kpgnn_stream_t stream);
+int kpgnn_head_linear_bwd(const kpgnn_head_linear_desc* d, kpgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Classification loss (csrc/class_loss.hip): F.nll_loss(F.log_softmax(logits, -1), y), which F.cross_entropy and
+ * nn.CrossEntropyLoss() reduce to (train_TU.py:45-46, train_EXP.py:81-82, train_CSL.py:41, train_SR.py:38).  One launch:
+ *   loss[0] = sum (reduction 1) or mean (reduction 0) over the counted rows of  logsumexp(logits[m,:]) - logits[m, y[m]]
+ *   dlogits[m,:] = (softmax(logits[m,:]) - onehot(y[m])) * (1 or 1 / count)         (NULL: skipped)
+ *   correct[0] = number of counted rows whose arg-max is y[m]                         (NULL: skipped)
+ * A row whose label is outside [0, C) is NOT counted, the way ignore_index = -100 is: no loss term, a zero gradient row, not
+ * in the mean's denominator, and the label is never used as an index.  This is deliberate: the framework asserts on the
+ * device for such a label, which takes the process down; here it is data.  Max-subtracted, one block, fixed summation order:
+ * bitwise reproducible.  C <= 1024 (KPGNN_ELIMIT beyond).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct kpgnn_nll_loss_desc {
+    int64_t M;                  /* rows (0: loss = 0 for sum, 0 / 0 for mean) */
+    int32_t C;                  /* classes */
+    int32_t reduction;          /* 0 = mean, 1 = sum */
+    const float* logits; int64_t logits_stride;   /* device [M,C] */
+    const int64_t* y;           /* device [M] labels */
+    float* loss;                /* device [1] */
+    float* dlogits; int64_t dlogits_stride;       /* device [M,C] (overwritten; NULL: skipped) */
+    int32_t* correct;           /* device [1] (NULL: skipped) */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= M; kpgnn_wgrad_desc explains); NULL: all M rows */
+} kpgnn_nll_loss_desc;
+
+int kpgnn_nll_loss(const kpgnn_nll_loss_desc* d, kpgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Projected peripheral-feature tables (csrc/enc_tables.hip): for every encoder e (a FeatureConcatEncoder: per-column
  * nn.Embedding -> concat -> Linear, layers/feature_encoder.py:37-67, gated by squash(pew / pcw), models/GNNs.py:172-179 /
  * :393-400 / :637-644) and every component c of it

@@ -286,6 +286,35 @@ class PoolDesc(ctypes.Structure):
     ]
 
 
+class AttnPoolDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("G", c_i32), ("D", c_i32),
+        ("graph_ptr", c_vp), ("x", c_vp), ("x_stride", c_i64), ("w", c_vp), ("bias", c_vp),
+        ("alpha", c_vp), ("out", c_vp), ("gout", c_vp), ("gx", c_vp), ("gx_stride", c_i64), ("dw", c_vp), ("db", c_vp),
+        ("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t),
+        ("n_dyn", c_vp),
+    ]
+
+
+class HeadLinearDesc(ctypes.Structure):
+    _fields_ = [
+        ("M", c_i64), ("O", c_i32), ("I", c_i32),
+        ("x", c_vp), ("x_stride", c_i64), ("w", c_vp), ("bias", c_vp), ("y", c_vp), ("y_stride", c_i64),
+        ("dy", c_vp), ("dy_stride", c_i64), ("dx", c_vp), ("dx_stride", c_i64), ("dw", c_vp), ("db", c_vp),
+        ("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t),
+        ("n_dyn", c_vp),
+    ]
+
+
+class NllLossDesc(ctypes.Structure):
+    _fields_ = [
+        ("M", c_i64), ("C", c_i32), ("reduction", c_i32),
+        ("logits", c_vp), ("logits_stride", c_i64), ("y", c_vp), ("loss", c_vp),
+        ("dlogits", c_vp), ("dlogits_stride", c_i64), ("correct", c_vp),
+        ("n_dyn", c_vp),
+    ]
+
+
 class DatasetView(ctypes.Structure):
     _fields_ = [
         ("K", c_i32), ("G", c_i32), ("node_ptr", c_vp), ("pair_ptr", c_vp), ("ent_ptr", c_vp),
@@ -360,6 +389,13 @@ SIGNATURES = {
     "kpgnn_enc_tables_bwd": (ctypes.c_int, [ctypes.POINTER(EncTablesDesc), c_vp]),
     "kpgnn_segment_pool_fwd": (ctypes.c_int, [ctypes.POINTER(PoolDesc), c_vp]),
     "kpgnn_segment_pool_bwd": (ctypes.c_int, [ctypes.POINTER(PoolDesc), c_vp]),
+    "kpgnn_attn_pool_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
+    "kpgnn_attn_pool_fwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),
+    "kpgnn_attn_pool_bwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),
+    "kpgnn_head_linear_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i32, c_i32]),
+    "kpgnn_head_linear_fwd": (ctypes.c_int, [ctypes.POINTER(HeadLinearDesc), c_vp]),
+    "kpgnn_head_linear_bwd": (ctypes.c_int, [ctypes.POINTER(HeadLinearDesc), c_vp]),
+    "kpgnn_nll_loss": (ctypes.c_int, [ctypes.POINTER(NllLossDesc), c_vp]),
     "kpgnn_stat_slot_bytes": (ctypes.c_size_t, [c_i32]),
     "kpgnn_stream_capture_id": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64)]),
     "kpgnn_attn_fwd": (ctypes.c_int, [ctypes.POINTER(AttnDesc), c_vp]),

@@ -15,8 +15,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .layers.gine import GINEConv
-from .ops import DictPeripheral, embedding_rows, enc_tables, segment_pool, table_gather_sum
-from .ops_dense import JKConcatLinear, batch_norm_act, jk_concat_linear_nograd, prepare_mlp_splits, score_head
+from .ops import DictPeripheral, attention_pool, embedding_rows, enc_tables, segment_pool, table_gather_sum
+from .ops_dense import JKConcatLinear, batch_norm_act, head_linear, jk_concat_linear_nograd, prepare_mlp_splits, score_head
 
 MAX_DICT_ROWS = 128  # peripheral dictionaries up to this many distinct tuples use the dictionary kernels
 
@@ -577,18 +577,132 @@ def _prepare_splits(layers, x):
             prepare_mlp_splits(mlps, x.size(0))
 
 
+# ------------------------------------------------------------------------------------------------ readouts and task heads
+def _num_graphs(batch, size):
+    return int(batch[-1].item()) + 1 if size is None else size
+
+
+def global_mean_pool(x, batch, size=None):
+    size = _num_graphs(batch, size)
+    if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32:
+        return segment_pool(x, batch, size, mean=True)
+    cnt = x.new_zeros(size).index_add_(0, batch, x.new_ones(batch.numel()))
+    return global_add_pool(x, batch, size) / cnt.clamp(min=1).unsqueeze(-1)
+
+
+def global_max_pool(x, batch, size=None):
+    size = _num_graphs(batch, size)
+    idx = batch.view(-1, 1).expand_as(x)
+    return x.new_full((size, x.size(1)), float("-inf")).scatter_reduce(0, idx, x, reduce="amax")
+
+
+class AttentionalAggregation(nn.Module):
+    """PyG's AttentionalAggregation(gate_nn=nn.Linear(hidden, 1)) as the reference heads build it
+    (models/GraphClassification.py:31-32): out[g] = sum_n softmax_g(gate_nn(x))[n] x[n].  state_dict keys gate_nn.weight /
+    gate_nn.bias, as PyG's module yields; the arithmetic is ops.attention_pool (one HIP launch forward)."""
+
+    def __init__(self, gate_nn):
+        super().__init__()
+        self.gate_nn = gate_nn
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.gate_nn.reset_parameters()
+
+    def forward(self, x, batch, size=None):
+        return attention_pool(x, batch, _num_graphs(batch, size), self.gate_nn)
+
+
+def make_pool(pooling_method, hidden_size):
+    """self.pool of the two graph-level heads (models/GraphRegression.py / GraphClassification.py:24-34): a function for
+    sum / mean / max, a module with parameters for attention.  Called as pool(x, batch, num_graphs)."""
+    if pooling_method == "sum":
+        return global_add_pool
+    if pooling_method == "mean":
+        return global_mean_pool
+    if pooling_method == "max":
+        return global_max_pool
+    if pooling_method == "attention":
+        return AttentionalAggregation(gate_nn=nn.Linear(hidden_size, 1))
+    raise ValueError("The pooling method not implemented")
+
+
 class GraphRegression(nn.Module):
-    """Pool + Linear head (reference models/GraphRegression.py:9-51); sum / mean / max pooling."""
+    """Pool + Linear head (reference models/GraphRegression.py:9-51); sum / mean / max / attention pooling."""
 
     def __init__(self, embedding_model, pooling_method):
         super().__init__()
         self.embedding_model = embedding_model
         self.JK, self.num_layer = embedding_model.JK, embedding_model.num_layer
         self.pooling_method = pooling_method
-        if pooling_method not in ("sum", "mean", "max"):
-            if pooling_method == "attention":
-                raise NotImplementedError("attention pooling is a PyG module")
-            raise ValueError("The pooling method not implemented")
+        self.pool = make_pool(pooling_method, embedding_model.hidden_size)
+        self.regressor = nn.Linear(embedding_model.hidden_size, 1)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.embedding_model.reset_parameters()
+        self.regressor.reset_parameters()
+        if self.pooling_method == "attention":
+            self.pool.reset_parameters()
+
+    def forward(self, data):
+        x = self.embedding_model(data)
+        return score_head(self.pool(x, data.batch, _get(data, "num_graphs")), self.regressor).squeeze()
+
+
+class GraphClassification(nn.Module):
+    """Pool + Linear classifier (reference models/GraphClassification.py:9-52): logits [num_graphs, output_size]."""
+
+    def __init__(self, embedding_model, pooling_method, output_size):
+        super().__init__()
+        self.embedding_model = embedding_model
+        hidden_size = embedding_model.hidden_size
+        self.JK, self.num_layer = embedding_model.JK, embedding_model.num_layer
+        self.pooling_method = pooling_method
+        self.pool = make_pool(pooling_method, hidden_size)
+        self.classifier = nn.Linear(hidden_size, output_size)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.embedding_model.reset_parameters()
+        self.classifier.reset_parameters()
+        if self.pooling_method == "attention":
+            self.pool.reset_parameters()
+
+    def forward(self, data):
+        x = self.embedding_model(data)
+        return head_linear(self.pool(x, data.batch, _get(data, "num_graphs")), self.classifier)
+
+
+class NodeClassification(nn.Module):
+    """Linear classifier on the node rows (reference models/NodeClassification.py:7-35): logits [num_nodes, output_size]."""
+
+    def __init__(self, embedding_model, output_size):
+        super().__init__()
+        self.embedding_model = embedding_model
+        hidden_size = embedding_model.hidden_size
+        self.JK, self.num_layer = embedding_model.JK, embedding_model.num_layer
+        # (the reference sizes the classifier for hidden_size * (num_layer + 1) inputs under JK == "concat", although its
+        #  bodies project the concatenation back to hidden_size: kept as it is so that checkpoints load)
+        width = hidden_size * (self.num_layer + 1) if self.JK == "concat" else hidden_size
+        self.classifier = nn.Linear(width, output_size)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.embedding_model.reset_parameters()
+        self.classifier.reset_parameters()
+
+    def forward(self, data):
+        return head_linear(self.embedding_model(data), self.classifier)
+
+
+class NodeRegression(nn.Module):
+    """Linear(hidden, 1) on the node rows (reference models/NodeRegression.py:7-29): one score per node."""
+
+    def __init__(self, embedding_model):
+        super().__init__()
+        self.embedding_model = embedding_model
+        self.JK, self.num_layer = embedding_model.JK, embedding_model.num_layer
         self.regressor = nn.Linear(embedding_model.hidden_size, 1)
         self.reset_parameters()
 
@@ -596,18 +710,5 @@ class GraphRegression(nn.Module):
         self.embedding_model.reset_parameters()
         self.regressor.reset_parameters()
 
-    def pool(self, x, batch, num_graphs=None):
-        size = int(batch[-1].item()) + 1 if num_graphs is None else num_graphs
-        if self.pooling_method == "sum":
-            return global_add_pool(x, batch, size)
-        if self.pooling_method == "mean":
-            if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32:
-                return segment_pool(x, batch, size, mean=True)
-            cnt = x.new_zeros(size).index_add_(0, batch, x.new_ones(batch.numel()))
-            return global_add_pool(x, batch, size) / cnt.clamp(min=1).unsqueeze(-1)
-        idx = batch.view(-1, 1).expand_as(x)
-        return x.new_full((size, x.size(1)), float("-inf")).scatter_reduce(0, idx, x, reduce="amax")
-
     def forward(self, data):
-        x = self.embedding_model(data)
-        return score_head(self.pool(x, data.batch, _get(data, "num_graphs")), self.regressor).squeeze()
+        return head_linear(self.embedding_model(data), self.regressor).squeeze()

@@ -1320,6 +1320,78 @@ def segment_pool(x, batch, num_graphs, mean=False):
     return SegmentPool.apply(x, batch.long() if batch.dtype != torch.int64 else batch, graph_ptr_of(batch, num_graphs), num_graphs, mean)
 
 
+class AttentionPool(torch.autograd.Function):
+    """PyG's AttentionalAggregation(gate_nn=nn.Linear(D, 1)) over the node ranges of a collated batch (kpgnn_attn_pool_*):
+    one launch forward, one plus a fixed-order reduce backward, no atomics."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, ptr, num_graphs):
+        x = _last_contig(x)
+        N, D = x.shape
+        w = weight.reshape(-1).contiguous()
+        if w.numel() != D:           # the kernel reads D gate weights
+            raise _lib.KpgnnError(f"attention_pool: x has {D} columns, the gate weight {w.numel()}")
+        out = torch.empty((num_graphs, D), dtype=torch.float32, device=x.device)
+        alpha = torch.empty((N,), dtype=torch.float32, device=x.device)
+        d = _lib.AttnPoolDesc()
+        d.N, d.G, d.D = N, num_graphs, D
+        d.n_dyn = dyn_ptr(N)
+        d.graph_ptr, d.x, d.x_stride, d.w, d.bias = ptr.data_ptr(), x.data_ptr(), x.stride(0), w.data_ptr(), _ptr(bias)
+        d.alpha, d.out = alpha.data_ptr(), out.data_ptr()
+        _lib.launch("kpgnn_attn_pool_fwd", x.device, ctypes.byref(d))
+        ctx.save_for_backward(x, w, ptr, alpha, out)
+        ctx.has_bias = bias is not None
+        ctx.wshape = weight.shape
+        ctx.mark_non_differentiable(alpha)
+        return out, alpha
+
+    @staticmethod
+    def backward(ctx, gout, _galpha):
+        x, w, ptr, alpha, out = ctx.saved_tensors
+        N, D = x.shape
+        G = out.shape[0]
+        dev = x.device
+        gout = gout.contiguous()
+        gx = torch.empty((N, D), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        dw = torch.empty((D,), dtype=torch.float32, device=dev)
+        db = torch.empty((1,), dtype=torch.float32, device=dev) if ctx.has_bias else None
+        nb = int(_lib.load().kpgnn_attn_pool_workspace_bytes(G, D))
+        ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=dev)
+        d = _lib.AttnPoolDesc()
+        d.N, d.G, d.D = N, G, D
+        d.n_dyn = dyn_ptr(N)
+        d.graph_ptr, d.x, d.x_stride, d.w = ptr.data_ptr(), x.data_ptr(), x.stride(0), w.data_ptr()
+        d.alpha, d.out, d.gout = alpha.data_ptr(), out.data_ptr(), gout.data_ptr()
+        d.gx, d.gx_stride, d.dw, d.db = _ptr(gx), D, dw.data_ptr(), _ptr(db)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), nb
+        _lib.launch("kpgnn_attn_pool_bwd", dev, ctypes.byref(d))
+        return gx, dw.view(ctx.wshape), db, None, None
+
+
+def attention_pool_reference(x, batch, num_graphs, gate_lin):
+    """The framework formulation (any device / dtype): softmax of gate_lin(x) within each graph, then the weighted sum."""
+    gate = gate_lin(x).reshape(-1)
+    idx = batch.long()
+    mx = gate.new_full((num_graphs,), float("-inf")).scatter_reduce(0, idx, gate.detach(), reduce="amax")
+    e = (gate - mx[idx]).exp()
+    alpha = e / (gate.new_zeros(num_graphs).index_add_(0, idx, e)[idx] + 1e-16)
+    return x.new_zeros((num_graphs, x.shape[1])).index_add_(0, idx, alpha.unsqueeze(-1) * x)
+
+
+def attention_pool(x, batch, num_graphs, gate_lin, return_alpha=False):
+    """AttentionalAggregation(gate_nn=gate_lin)(x, batch): out[g] = sum_n softmax_g(gate_lin(x))[n] x[n].  fp32 device rows up to
+    256 floats wide take the HIP kernels; anything else the framework formulation."""
+    if (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[1] <= 256 and gate_lin.out_features == 1
+            and gate_lin.in_features == x.shape[1] and gate_lin.weight.dtype == torch.float32):
+        # (a width mismatch goes to the framework formulation below, whose gate_lin(x) raises the framework's shape error)
+        b = batch.long() if batch.dtype != torch.int64 else batch
+        out, alpha = AttentionPool.apply(x, gate_lin.weight, gate_lin.bias, graph_ptr_of(b, num_graphs), num_graphs)
+        return (out, alpha) if return_alpha else out
+    assert not return_alpha
+    refuse_dynamic_rows("attention readout on the framework path", x.shape[0])
+    return attention_pool_reference(x, batch, num_graphs, gate_lin)
+
+
 # ------------------------------------------------------------------------------------------------ projected tables
 class EncTables(torch.autograd.Function):
     """(table [R,H], bias [H]) of the projected peripheral-feature tables (kpgnn_enc_tables_*): for encoder e with

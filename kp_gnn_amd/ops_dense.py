@@ -915,3 +915,132 @@ def regression_loss(score, y, kind="l1"):
         return RegressionLoss.apply(score, y, 0 if kind == "l1" else 1)
     d = score.squeeze() - y.squeeze()
     return d.abs().mean() if kind == "l1" else (d * d).mean()
+
+
+# ------------------------------------------------------------------------------------------- narrow-output Linear
+class HeadLinear(torch.autograd.Function):
+    """nn.Linear with out_features <= 32 (the classifiers of models/GraphClassification.py:37 / NodeClassification.py:21-24 and
+    the node regressor of NodeRegression.py:18) on kpgnn_head_linear_fwd / _bwd: one launch forward, one plus a fixed-order
+    reduce backward, over graph rows or node rows alike."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = x if x.stride(-1) == 1 else x.contiguous()
+        w = weight.contiguous()
+        M, I = x.shape
+        O = w.shape[0]
+        if w.shape[1] != I:          # the kernel indexes W as [O, I]
+            raise _lib.KpgnnError(f"head_linear: x has {I} columns, the weight {w.shape[1]}")
+        y = torch.empty((M, O), dtype=torch.float32, device=x.device)
+        d = _lib.HeadLinearDesc()
+        d.M, d.O, d.I = M, O, I
+        d.n_dyn = dyn_ptr(M)
+        d.x, d.x_stride, d.w, d.bias, d.y, d.y_stride = x.data_ptr(), x.stride(0), w.data_ptr(), _ptr(bias), y.data_ptr(), O
+        _lib.launch("kpgnn_head_linear_fwd", x.device, ctypes.byref(d))
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        M, I = x.shape
+        O = w.shape[0]
+        dev = x.device
+        dy = dy if dy.stride(-1) == 1 else dy.contiguous()
+        dx = torch.empty((M, I), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        dw = torch.empty((O, I), dtype=torch.float32, device=dev)
+        db = torch.empty((O,), dtype=torch.float32, device=dev) if ctx.has_bias else None
+        nb = int(_lib.load().kpgnn_head_linear_workspace_bytes(M, O, I))
+        ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=dev)
+        d = _lib.HeadLinearDesc()
+        d.M, d.O, d.I = M, O, I
+        d.n_dyn = dyn_ptr(M)
+        d.x, d.x_stride, d.w = x.data_ptr(), x.stride(0), w.data_ptr()
+        d.dy, d.dy_stride, d.dx, d.dx_stride = dy.data_ptr(), dy.stride(0), _ptr(dx), I
+        d.dw, d.db, d.workspace, d.workspace_bytes = dw.data_ptr(), _ptr(db), ws.data_ptr(), nb
+        _lib.launch("kpgnn_head_linear_bwd", dev, ctypes.byref(d))
+        return dx, dw, db
+
+
+def head_linear(x, lin):
+    """lin(x) for an nn.Linear with at most 32 outputs and at most 1024 inputs on fp32 device rows (HeadLinear); any other
+    shape / device / dtype goes to the module itself."""
+    if (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and lin.weight.dtype == torch.float32
+            and lin.out_features <= 32 and lin.in_features <= 1024 and x.shape[0] >= 1
+            and x.shape[1] == lin.in_features):       # (a width mismatch goes to the module, which raises the framework's shape error)
+        return HeadLinear.apply(x, lin.weight, lin.bias)
+    refuse_dynamic_rows("nn.Linear outside the narrow-output kernel's shapes", x.shape[0])
+    return lin(x)
+
+
+# ------------------------------------------------------------------------------------------- classification loss
+def _nll_launch(logits, y, reduction, want_grad, want_correct):
+    """One kpgnn_nll_loss launch: (loss, dlogits or None, correct or None)."""
+    assert reduction in ("mean", "sum")
+    lg = logits if logits.stride(-1) == 1 else logits.contiguous()
+    t = y.reshape(-1).to(torch.int64).contiguous()
+    M, C = lg.shape
+    assert t.numel() == M and M >= 1
+    dev = lg.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dl = torch.empty((M, C), dtype=torch.float32, device=dev) if want_grad else None
+    correct = torch.empty((), dtype=torch.int32, device=dev) if want_correct else None
+    d = _lib.NllLossDesc()
+    d.M, d.C, d.reduction = M, C, 0 if reduction == "mean" else 1
+    d.n_dyn = dyn_ptr(M)
+    d.logits, d.logits_stride, d.y, d.loss = lg.data_ptr(), lg.stride(0), t.data_ptr(), loss.data_ptr()
+    d.dlogits, d.dlogits_stride, d.correct = _ptr(dl), C, _ptr(correct)
+    _lib.launch("kpgnn_nll_loss", dev, ctypes.byref(d))
+    return loss, dl, correct
+
+
+def _nll_native(logits, y):
+    return (logits.is_cuda and logits.dim() == 2 and logits.dtype == torch.float32 and logits.shape[1] <= 1024
+            and logits.shape[0] >= 1 and y.numel() == logits.shape[0])
+
+
+class ClassificationLoss(torch.autograd.Function):
+    """F.nll_loss(F.log_softmax(logits, -1), y) (train_TU.py:45-46, train_EXP.py:81-82; nn.CrossEntropyLoss() of train_CSL.py:41 /
+    train_SR.py:38 is the same) with its gradient computed by the same launch (kpgnn_nll_loss).  A label outside [0, C) is
+    skipped the way ignore_index = -100 is (include/kpgnn.h)."""
+
+    @staticmethod
+    def forward(ctx, logits, y, reduction):
+        loss, dl, _ = _nll_launch(logits, y, reduction, ctx.needs_input_grad[0], False)
+        ctx.save_for_backward(dl)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        (dl,) = ctx.saved_tensors
+        return dl * gout if dl is not None else None, None, None
+
+
+def classification_loss(logits, y, reduction="mean"):
+    """The classification scripts' loss on a batch of logits [M, C] and int labels [M]."""
+    if _nll_native(logits, y):
+        return ClassificationLoss.apply(logits, y, reduction)
+    return F.nll_loss(F.log_softmax(logits, dim=-1), y.reshape(-1).long(), reduction=reduction)
+
+
+def classification_loss_and_grad(logits, y, reduction="mean"):
+    """(loss, d loss / d logits) from the one launch, for a caller that seeds the backward pass itself
+    (torch.autograd.grad(logits, params, grad_outputs=dlogits)), as regression_loss_and_grad."""
+    assert _nll_native(logits, y)
+    with torch.no_grad():
+        loss, dl, _ = _nll_launch(logits.detach(), y, reduction, True, False)
+    return loss, dl
+
+
+def classification_eval(logits, y):
+    """(sum of the per-row losses, number of rows whose arg-max is the label) from one launch: val() / test() of the
+    classification scripts (train_TU.py:66-67: pred.eq(y).sum())."""
+    if _nll_native(logits, y):
+        with torch.no_grad():
+            loss, _, correct = _nll_launch(logits.detach(), y, "sum", False, True)
+        return loss, correct
+    t = y.reshape(-1).long()
+    with torch.no_grad():
+        return (F.nll_loss(F.log_softmax(logits, dim=-1), t, reduction="sum"),
+                (logits.argmax(dim=-1) == t).sum().to(torch.int32))
