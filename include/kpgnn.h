@@ -290,6 +290,29 @@ typedef struct kpgnn_agg_fwd_desc {
 
 int kpgnn_aggregate_fwd(const kpgnn_agg_fwd_desc* d, kpgnn_stream_t stream);
 
+/* The PULL form of the backward gather as an entry of its own: with rowptr / col the (source, hop)-keyed CSR and slab[k] hop
+ * k's [N,D] slab (row stride slab_sn) of dL/dS of the layer that read the state at hop slot k,
+ *   hout[i,:] = hinit[i,:] + hinit2[i,:] + sum_k sum_{a in segment (i,k)} slab[k][col[a],:]
+ * (pairs in list order into a per-hop sum, then the hops in order, after hinit and then hinit2) - exactly what
+ * kpgnn_aggregate_fwd writes for mode SUM, use_tables = 0, x_slot = slab and theta = 1, bit for bit.  Rows of 36 to 256
+ * columns with D % 4 == 0, 16-byte aligned operands and K below the row's lane count (16 lanes up to D = 64, 32 up to 128,
+ * 64 beyond) run a kernel specialised for this case (no epilogue, no theta: more resident waves per SIMD); every other row
+ * shape runs the generic kernel with unit weights. */
+typedef struct kpgnn_pull_gather_desc {
+    int32_t N, K, D;            /* nodes (capacity with n_dyn), hop slabs read (<= 16, <= K_csr), row width */
+    int32_t K_csr;              /* hop slots per node in rowptr */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= N); NULL: all N rows.  Rows beyond it are not written */
+    const int32_t* rowptr;      /* device, [N*K_csr+1], keyed by (source, hop) */
+    const int32_t* col;         /* device, [A] */
+    const float* slab[16];      /* device, slab[k]: [N,D] with row stride slab_sn, k < K */
+    int64_t slab_sn;
+    const float* hinit;         /* device [N,D] contiguous or NULL; may be hout itself */
+    const float* hinit2;        /* device [N,D] contiguous or NULL */
+    float* hout;                /* device [N,D] contiguous */
+} kpgnn_pull_gather_desc;
+
+int kpgnn_khop_pull_gather(const kpgnn_pull_gather_desc* d, kpgnn_stream_t stream);
+
 /* How many kpgnn_aggregate_fwd calls of this process were served by the LDS-staged kernel (graph_ptr given and every
  * condition above met).  A host-side counter: the choice of kernel leaves no other trace, so a test of that kernel reads it
  * before and after its call. */

@@ -40,6 +40,15 @@ class AggFwdDesc(ctypes.Structure):
     ]
 
 
+class PullGatherDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i32), ("K", c_i32), ("D", c_i32), ("K_csr", c_i32),
+        ("n_dyn", c_vp), ("rowptr", c_vp), ("col", c_vp),
+        ("slab", c_vp * 16), ("slab_sn", c_i64),
+        ("hinit", c_vp), ("hinit2", c_vp), ("hout", c_vp),
+    ]
+
+
 class AggBwdDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i32), ("K", c_i32), ("D", c_i32), ("K_csr", c_i32), ("mode", c_i32),
@@ -351,6 +360,7 @@ SIGNATURES = {
                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp,
                                        c_vp, ctypes.c_size_t, c_vp]),
     "kpgnn_aggregate_fwd": (ctypes.c_int, [ctypes.POINTER(AggFwdDesc), c_vp]),
+    "kpgnn_khop_pull_gather": (ctypes.c_int, [ctypes.POINTER(PullGatherDesc), c_vp]),
     "kpgnn_agg_lds_launch_count": (c_i64, []),
     "kpgnn_aggregate_bwd": (ctypes.c_int, [ctypes.POINTER(AggBwdDesc), c_vp]),
     "kpgnn_table_grad_workspace_bytes": (ctypes.c_size_t, [c_i32] * 7),

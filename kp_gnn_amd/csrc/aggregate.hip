@@ -79,13 +79,24 @@ struct FwdParams {
 // FAST: the KP-GIN+ training configuration (GELU epilogue, fused geometric combine, dictionary P, S saved) with its
 // epilogue switches resolved at compile time.
 // BF (FAST only): the gathered hop slots (xs) and the saved S (`pre`) are bf16 rows; sums, tables, theta, P, hout fp32.
-template <int VEC, int G, bool GCN, int TAB, bool FAST = false, bool BF = false>
-__global__ void __launch_bounds__(kBlock, FAST ? 5 : 4)
+// PULL: the pull form of the backward gather (kpgnn_khop_pull_gather) resolved at compile time - mode SUM, per-hop slabs,
+// hop sums added with unit weights (no theta), none of the epilogue operands, K < G so the row pointers sit in the lanes.
+// The generic instantiation carried the whole epilogue's registers for it (109 VGPRs, 4 waves per SIMD) and a load of the
+// all-ones theta row per (node, hop); this one needs 66 registers.
+#ifndef KPGNN_PULL_WAVES
+#define KPGNN_PULL_WAVES 7      // blocks of 256 threads per CU = waves per SIMD (profiles/pull/README.md: 5, 6, 7 measured)
+#endif
+#ifndef KPGNN_PULL_PF
+#define KPGNN_PULL_PF 4         // rows requested one hop ahead
+#endif
+template <int VEC, int G, bool GCN, int TAB, bool FAST = false, bool BF = false, bool PULL = false>
+__global__ void __launch_bounds__(kBlock, PULL ? KPGNN_PULL_WAVES : FAST ? 5 : 4)
 agg_fwd_kernel(const FwdParams p) {
+    static_assert(!PULL || (!GCN && TAB == 0 && !FAST && !BF), "the pull form gathers fp32 slabs without tables");
     // (a local: writing to the by-value argument would move the whole struct - pointer arrays indexed at run time - to scratch)
     const int N_live = live_rows(p.N, p.n_dyn);
-    const int MODE = FAST ? (int)KPGNN_MODE_GINPLUS : p.mode;
-    const bool COMBINE = FAST ? true : p.combine != 0;
+    const int MODE = PULL ? (int)KPGNN_MODE_SUM : FAST ? (int)KPGNN_MODE_GINPLUS : p.mode;
+    const bool COMBINE = (FAST || PULL) ? true : p.combine != 0;
     extern __shared__ __attribute__((aligned(16))) float lds_tab[];
     const int D = p.D;
     const float* thp = p.theta;
@@ -134,7 +145,7 @@ agg_fwd_kernel(const FwdParams p) {
     const int sg_lane0 = lane - sl;        // first lane of this sub-group inside its wave
     const int c0 = sl * VEC;
     const bool col_ok = c0 < D;
-    const float eps1 = 1.0f + (p.eps ? p.eps[0] : 0.0f);
+    const float eps1 = 1.0f + (!PULL && p.eps ? p.eps[0] : 0.0f);
     const int64_t num_tiles = ((int64_t)N_live + NODES - 1) / NODES;
     constexpr uint32_t XB = BF ? 2u : 4u;                       // bytes per stored element of a gathered row
     const uint32_t xrow_b = (uint32_t)p.x_sn * XB, trow_b = (uint32_t)D * 4u;   // (host: N * x_sn * 4 < 2^32)
@@ -156,11 +167,11 @@ agg_fwd_kernel(const FwdParams p) {
         // DEPENDENT round trips (row pointer -> pair list -> neighbour rows, then uid -> dictionary row).  So the node's
         // K+1 row pointers, its K dictionary ids and its whole pair list (all hops, one chunk of G pairs at a time -
         // a ZINC node has ~21) are fetched up front by the lanes of the sub-group and handed out with ds_bpermute.
-        const bool lane_meta = G > p.K;                    // K+1 row pointers fit the sub-group's lanes
+        const bool lane_meta = PULL ? true : G > p.K;      // K+1 row pointers fit the sub-group's lanes (PULL: the host checked)
         int myrp = 0, myuid = 0;
         if (lane_meta) {
             myrp = rp[sl <= p.K ? sl : p.K];
-            if (FAST || (p.uid && !p.periph)) myuid = p.uid[i * p.uid_stride + (sl < p.K ? sl : 0)];
+            if (!PULL && (FAST || (p.uid && !p.periph))) myuid = p.uid[i * p.uid_stride + (sl < p.K ? sl : 0)];
         }
         int beg = lane_meta ? __shfl(myrp, sg_lane0) : rp[0];
         const int end_all = lane_meta ? __shfl(myrp, sg_lane0 + p.K) : rp[p.K];
@@ -176,14 +187,14 @@ agg_fwd_kernel(const FwdParams p) {
         }
         // Rows of the NEXT hop's first pairs are requested before the current hop is summed and finished, so the one
         // dependent round trip left per hop (the neighbour rows) overlaps the previous hop's epilogue.
-        constexpr int PF = G >= 32 ? 4 : 2;   // (narrow rows, 4+ nodes per wave: deeper prefetch measured slower, 60 vs 49 us at D = 13)
+        constexpr int PF = G < 32 ? 2 : PULL ? KPGNN_PULL_PF : 4;   // (narrow rows, 4+ nodes per wave: deeper prefetch measured slower, 60 vs 49 us at D = 13)
         V<VEC> pr[PF];
         uint32_t prb[PF];
         int prn = 0;
         auto prefetch = [&](int kk, int bpos, int bend) {
             prn = min(PF, min(bend, cbase + G) - bpos);
             if (prn < 0) prn = 0;
-            const char* xb = reinterpret_cast<const char*>(p.x ? p.x + (int64_t)kk * p.x_sk : p.xs[kk]);
+            const char* xb = reinterpret_cast<const char*>(!PULL && p.x ? p.x + (int64_t)kk * p.x_sk : p.xs[kk]);
 #pragma unroll
             for (int u = 0; u < PF; ++u) {
                 if (u < prn) {
@@ -199,8 +210,8 @@ agg_fwd_kernel(const FwdParams p) {
         for (int k = 0; k < p.K; ++k) {
             const int end = end_next;
             if (GCN && k + 1 < p.K) end_next = lane_meta ? __shfl(myrp, sg_lane0 + k + 2) : rp[k + 2];
-            const int uk = lane_meta ? __shfl(myuid, sg_lane0 + k) : 0;     // (shuffles need the whole sub-group active)
-            const float* xk = (p.x ? p.x + (int64_t)k * p.x_sk : p.xs[k]) + c0;
+            const int uk = !PULL && lane_meta ? __shfl(myuid, sg_lane0 + k) : 0;     // (shuffles need the whole sub-group active)
+            const float* xk = (!PULL && p.x ? p.x + (int64_t)k * p.x_sk : p.xs[k]) + c0;
             const float* tab = k == 0 ? tab0 : tabk;
             V<VEC> acc = V<VEC>::zero();
             float wacc = 0.f;  // GCN: sum of edge weights of the segment (for the constant x-bias term)
@@ -209,7 +220,7 @@ agg_fwd_kernel(const FwdParams p) {
             // (ds_bpermute) and adds the lane's column offset: no 64-bit / quarter-rate integer math per pair
             // (it was ~20 of the ~35 VALU slots a pair cost).  Two pairs per trip + a one-pair tail: segments hold
             // 2.7 pairs on average, a 4-deep body mostly ran masked.
-            const char* xkb = reinterpret_cast<const char*>(p.x ? p.x + (int64_t)k * p.x_sk : p.xs[k]);   // wave-uniform
+            const char* xkb = reinterpret_cast<const char*>(!PULL && p.x ? p.x + (int64_t)k * p.x_sk : p.xs[k]);   // wave-uniform
             const char* tabb = reinterpret_cast<const char*>(tab);
             if (!GCN) {
                 // (sum the prefetched rows first, then reuse their registers for the next hop's prefetch: a copy would
@@ -310,6 +321,7 @@ agg_fwd_kernel(const FwdParams p) {
             const int seglen = end - beg;
             beg = end;
             if (!col_ok) continue;
+            if (PULL) { hsum.add(acc); continue; }      // (h + 1 * v as the generic launch with theta = 1 rounded it)
             // ---- epilogue for (i,k)
             V<VEC> v = acc;
             // constant row added to every x row of hops >= 1: hopk_node_path_emb(pe_attr == 0), KPGIN.py:92-94
@@ -336,8 +348,11 @@ agg_fwd_kernel(const FwdParams p) {
             }
             if (MODE == KPGNN_MODE_GIN) { V<VEC> xs = V<VEC>::load(xk + i * p.x_sn); xs.add(xb); v.fma(eps1, xs); }
             if (COMBINE) {
-                const V<VEC> th = V<VEC>::load(thp + k * D + c0);
-                for (int q = 0; q < VEC; ++q) hsum.v[q] = fmaf(th.v[q], v.v[q], hsum.v[q]);
+                if (!FAST && !thp) hsum.add(v);         // (unit weights: the pull form on a row shape without a PULL instantiation)
+                else {
+                    const V<VEC> th = V<VEC>::load(thp + k * D + c0);
+                    for (int q = 0; q < VEC; ++q) hsum.v[q] = fmaf(th.v[q], v.v[q], hsum.v[q]);
+                }
             } else {
                 v.store_stream(p.out + i * p.o_sn + (int64_t)k * p.o_sk + c0);
             }
@@ -574,14 +589,15 @@ unsigned pick_grid(int64_t num_tiles, int blocks_per_cu) {
     return (unsigned)(g > 0 ? g : 1);
 }
 
-template <int VEC, int G, bool GCN, int TAB, bool FAST = false, bool BF = false>
+template <int VEC, int G, bool GCN, int TAB, bool FAST = false, bool BF = false, bool PULL = false>
 int launch_fwd(const FwdParams& p, size_t lds, hipStream_t s) {
     const int64_t tiles = ((int64_t)p.N + (kBlock / G) - 1) / (kBlock / G);
     if (lds > 64 * 1024)
-        KPGNN_HIP_TRY(ensure_dynamic_lds((const void*)agg_fwd_kernel<VEC, G, GCN, TAB, FAST, BF>, lds));
-    const int nb = resident_blocks(agg_fwd_kernel<VEC, G, GCN, TAB, FAST, BF>, kBlock, lds);
+        KPGNN_HIP_TRY(ensure_dynamic_lds((const void*)agg_fwd_kernel<VEC, G, GCN, TAB, FAST, BF, PULL>, lds));
+    int nb = resident_blocks(agg_fwd_kernel<VEC, G, GCN, TAB, FAST, BF, PULL>, kBlock, lds);
+    if (PULL && nb > KPGNN_PULL_WAVES) nb = KPGNN_PULL_WAVES;     // (the registers allow 7 whatever the bound says: the grid holds it to the measured best)
     const unsigned grid = pick_grid(tiles, nb > 0 ? nb : 4);
-    hipLaunchKernelGGL((agg_fwd_kernel<VEC, G, GCN, TAB, FAST, BF>), dim3(grid), dim3(kBlock), lds, s, p);
+    hipLaunchKernelGGL((agg_fwd_kernel<VEC, G, GCN, TAB, FAST, BF, PULL>), dim3(grid), dim3(kBlock), lds, s, p);
     KPGNN_LAUNCH_CHECK("agg_fwd_kernel");
     return KPGNN_OK;
 }
@@ -731,6 +747,43 @@ extern "C" int kpgnn_aggregate_fwd(const kpgnn_agg_fwd_desc* d, kpgnn_stream_t s
     hipStream_t s = (hipStream_t)stream;
     return dispatch_row_shape<64>(vec, row_lanes(d->D, vec), "aggregate_fwd",
                                   [&](auto VV, auto G) { return launch_fwd_mode<VV.value, G.value>(p, tab, lds, s); });
+}
+
+extern "C" int kpgnn_khop_pull_gather(const kpgnn_pull_gather_desc* d, kpgnn_stream_t stream) {
+    KPGNN_REQUIRE(d != nullptr, "khop_pull_gather: NULL descriptor");
+    KPGNN_REQUIRE(d->N >= 0 && d->K >= 1 && d->K <= 16 && d->D >= 1 && d->K_csr >= d->K, "khop_pull_gather: bad N=%d K=%d D=%d K_csr=%d",
+                  d->N, d->K, d->D, d->K_csr);
+    if ((int64_t)d->N * d->K_csr >= ((int64_t)1 << 31)) return fail(KPGNN_ELIMIT, "khop_pull_gather: N*K exceeds int32");
+    if (d->N == 0) return KPGNN_OK;
+    KPGNN_REQUIRE(d->rowptr != nullptr, "khop_pull_gather: NULL rowptr");      // (col may be NULL for a batch without pairs)
+    KPGNN_REQUIRE(d->hout != nullptr, "khop_pull_gather: NULL output");
+    for (int k = 0; k < d->K; ++k) KPGNN_REQUIRE(d->slab[k] != nullptr, "khop_pull_gather: NULL slab[%d]", k);
+    if ((uint64_t)d->N * (uint64_t)d->slab_sn * 4u >= (1ull << 32))
+        return fail(KPGNN_ELIMIT, "khop_pull_gather: N * slab row stride = %lld floats exceeds the 32-bit byte offsets of the gather", (long long)d->N * d->slab_sn);
+    FwdParams p = {};
+    p.N = d->N; p.n_dyn = d->n_dyn; p.K = d->K; p.D = d->D; p.K_csr = d->K_csr;
+    p.mode = KPGNN_MODE_SUM; p.combine = 1;         // theta stays NULL: unit weights
+    p.rowptr = d->rowptr; p.col = d->col;
+    p.x_sn = d->slab_sn;
+    p.hout = d->hout; p.hinit = d->hinit; p.hinit2 = d->hinit2;
+    uintptr_t slot_bits = 0;            // (as in kpgnn_aggregate_fwd: the least aligned slab decides the vector width)
+    for (int k = 0; k < d->K; ++k) {
+        p.xs[k] = d->slab[k];
+        slot_bits |= (uintptr_t)p.xs[k] & 15;
+    }
+    const void* slot_align = (const void*)(slot_bits | 16);
+    const int vec = row_vec(d->D, {slot_align, d->hout, d->hinit, d->hinit2}, {d->slab_sn});
+    const int lanes = (d->D + vec - 1) / vec;
+    if (lanes > 64) return fail(KPGNN_ELIMIT, "khop_pull_gather: D=%d with %d-wide access needs %d lanes > 64", d->D, vec, lanes);
+    hipStream_t s = (hipStream_t)stream;
+    return dispatch_row_shape<64>(vec, row_lanes(d->D, vec), "khop_pull_gather", [&](auto VV, auto G) {
+        // the specialisation exists for what ops.pull_applies lets through (16-byte lanes) and keeps the K + 1 row pointers of a
+        // node in its sub-group's lanes; every other row shape runs the generic instantiation with unit weights (same sums)
+        if constexpr (VV.value == 4 && G.value >= 16) {
+            if (G.value > d->K) return launch_fwd<4, G.value, false, 0, false, false, true>(p, 0, s);
+        }
+        return launch_fwd<VV.value, G.value, false, 0>(p, 0, s);
+    });
 }
 
 extern "C" int kpgnn_aggregate_bwd(const kpgnn_agg_bwd_desc* d, kpgnn_stream_t stream) {

@@ -271,7 +271,6 @@ def aggregate_fwd_raw(csr, k_act, mode, x, table0, tablek, periph, eps, theta, x
 
 
 PULL_GATHER = True      # (tests switch it off to compare with the read-modify-write form of the backward gather)
-_ones_cache = {}
 
 
 def pull_applies(N, D, dtype=torch.float32):
@@ -281,29 +280,24 @@ def pull_applies(N, D, dtype=torch.float32):
 
 
 def khop_pull_gather(csr, slabs, hinit, hinit2=None):
-    """A state's whole K-hop gradient in ONE launch (kpgnn_aggregate_fwd with the (source, hop)-keyed CSR, mode SUM, theta = 1
-    and `hinit`): out[i] = hinit[i] + sum_k sum_{j in N_k(i)} slabs[k][j], where slabs[k] is hop k's [N,D] slab of dL/dS of the
+    """A state's whole K-hop gradient in ONE launch (kpgnn_khop_pull_gather over the (source, hop)-keyed CSR):
+    out[i] = hinit[i] + sum_k sum_{j in N_k(i)} slabs[k][j], where slabs[k] is hop k's [N,D] slab of dL/dS of the
     layer that read the state at hop slot k.  Replaces one read-modify-write of the state's gradient per reader (36 per step
     at K = L = 8: agg_bwd moved 273 MB per launch for 183 MB of gathered rows) by one write per state."""
     K = len(slabs)
     N, D = slabs[0].shape
     dev = slabs[0].device
-    key = (dev, D)
-    ones = _ones_cache.get(key)
-    if ones is None:
-        ones = _ones_cache[key] = torch.ones((16, D), dtype=torch.float32, device=dev)
     out = hinit if hinit is not None else torch.empty((N, D), dtype=torch.float32, device=dev)
-    d = _lib.AggFwdDesc()
-    d.N, d.K, d.D, d.K_csr, d.mode = N, K, D, csr.K, MODE_SUM
+    d = _lib.PullGatherDesc()
+    d.N, d.K, d.D, d.K_csr = N, K, D, csr.K
     d.n_dyn = dyn_ptr(N)
-    d.use_tables = 0
-    d.rowptr, d.col, d.code = csr.rowptr_src.data_ptr(), csr.col_src.data_ptr(), csr.code_src.data_ptr()
-    d.x_sn = D
+    d.rowptr, d.col = csr.rowptr_src.data_ptr(), csr.col_src.data_ptr()
+    d.slab_sn = D
     for k, t in enumerate(slabs):
         assert t.shape == (N, D) and t.is_contiguous() and t.dtype == torch.float32
-        d.x_slot[k] = t.data_ptr()
-    d.theta, d.hout, d.hinit, d.hinit2 = ones.data_ptr(), out.data_ptr(), _ptr(hinit), _ptr(hinit2)
-    _lib.launch("kpgnn_aggregate_fwd", dev, ctypes.byref(d), timed=("agg_bwd", lambda: algorithmic_bytes(
+        d.slab[k] = t.data_ptr()
+    d.hout, d.hinit, d.hinit2 = out.data_ptr(), _ptr(hinit), _ptr(hinit2)
+    _lib.launch("kpgnn_khop_pull_gather", dev, ctypes.byref(d), timed=("agg_bwd", lambda: algorithmic_bytes(
         csr, K, D, 1, 0, extra_nd=1 + (hinit is not None) + (hinit2 is not None))))
     return out
 
