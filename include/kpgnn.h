@@ -843,6 +843,28 @@ int kpgnn_segment_pool_fwd(const kpgnn_pool_desc* d, kpgnn_stream_t stream);
 int kpgnn_segment_pool_bwd(const kpgnn_pool_desc* d, kpgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Virtual node (csrc/virtual_node.hip; models/GNNs.py:196-199,227-230: h + vn[batch], global_add_pool(h) + vn):
+ *   out[n,:]    = x[n,:] + v[g,:]               for the nodes n of graph g (graph_ptr[g] .. graph_ptr[g+1])
+ *   pooled[g,:] = sum_n out[n,:] + v[g,:]       (optional; an empty graph gives v[g,:])
+ * One launch, x read once, out written once, rows added in node order (bitwise reproducible, no atomics).  The work is driven
+ * by graph_ptr: a row at or beyond graph_ptr[G] (and beyond *n_dyn when given) is neither read nor written.
+ * The backward is the same entry: with gout = dL/dout and gp = dL/dpooled, gx[n] = gout[n] + gp[g] and
+ * gv[g] = sum_n gx[n] + gp[g], i.e. (x := gout, v := gp) -> (out := gx, pooled := gv).  D <= 256 (KPGNN_ELIMIT beyond).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct kpgnn_vn_desc {
+    int64_t N;                  /* node rows of x / out */
+    int32_t G, D;               /* graphs, feature width */
+    const int32_t* graph_ptr;   /* device [G+1], non-decreasing, graph_ptr[G] == the live node count */
+    const float* x; int64_t x_stride;      /* device [N,D] */
+    const float* v; int64_t v_stride;      /* device [G,D]; stride 0: one row for every graph */
+    float* out; int64_t out_stride;        /* device [N,D]; must not overlap x */
+    float* pooled;              /* device [G,D] contiguous, or NULL: not wanted */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= N; kpgnn_wgrad_desc explains); NULL: all N rows */
+} kpgnn_vn_desc;
+
+int kpgnn_vn_add_pool(const kpgnn_vn_desc* d, kpgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Attention readout (csrc/attn_pool.hip): PyG's AttentionalAggregation(gate_nn = nn.Linear(D, 1)) over the contiguous node
  * ranges of graph_ptr (models/GraphClassification.py:31-32, models/GraphRegression.py "attention"):
  *   gate[n] = x[n] . w + bias[0]      alpha[n] = exp(gate[n] - max_g) / (sum_{m in g} exp(gate[m] - max_g) + 1e-16)

@@ -295,6 +295,15 @@ class PoolDesc(ctypes.Structure):
     ]
 
 
+class VnDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("G", c_i32), ("D", c_i32),
+        ("graph_ptr", c_vp), ("x", c_vp), ("x_stride", c_i64), ("v", c_vp), ("v_stride", c_i64),
+        ("out", c_vp), ("out_stride", c_i64), ("pooled", c_vp),
+        ("n_dyn", c_vp),
+    ]
+
+
 class AttnPoolDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i64), ("G", c_i32), ("D", c_i32),
@@ -399,6 +408,7 @@ SIGNATURES = {
     "kpgnn_enc_tables_bwd": (ctypes.c_int, [ctypes.POINTER(EncTablesDesc), c_vp]),
     "kpgnn_segment_pool_fwd": (ctypes.c_int, [ctypes.POINTER(PoolDesc), c_vp]),
     "kpgnn_segment_pool_bwd": (ctypes.c_int, [ctypes.POINTER(PoolDesc), c_vp]),
+    "kpgnn_vn_add_pool": (ctypes.c_int, [ctypes.POINTER(VnDesc), c_vp]),
     "kpgnn_attn_pool_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "kpgnn_attn_pool_fwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),
     "kpgnn_attn_pool_bwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),

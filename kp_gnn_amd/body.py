@@ -15,8 +15,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .layers.gine import GINEConv
-from .ops import DictPeripheral, attention_pool, embedding_rows, enc_tables, segment_pool, table_gather_sum
-from .ops_dense import JKConcatLinear, batch_norm_act, head_linear, jk_concat_linear_nograd, prepare_mlp_splits, score_head
+from .ops import (DictPeripheral, attention_pool, embedding_rows, enc_tables, refuse_dynamic_rows, segment_pool, table_gather_sum,
+                  virtual_node_add)
+from .ops_dense import (JKConcatLinear, batch_norm_act, head_linear, jk_concat_linear_nograd, mlp_linear_bn_relu_x2,
+                        prepare_mlp_splits, score_head)
 
 MAX_DICT_ROWS = 128  # peripheral dictionaries up to this many distinct tuples use the dictionary kernels
 
@@ -358,13 +360,29 @@ class _KHopBody(nn.Module):
             return DictPeripheral(ptab, uid)
         return table_gather_sum(table, bias, idx, col_offset).view(num_nodes, -1, W)
 
-    def _vn_init(self, batch, edge_index):
-        idx = torch.zeros(int(batch[-1].item()) + 1, dtype=edge_index.dtype, device=edge_index.device)
-        return self.virtualnode_embedding(idx)
+    def _vn_init(self, data, batch):
+        """The virtual node's initial rows [G,H]: the one embedding row, expanded (row stride 0 - nothing is materialised, and
+        the gradient of the embedding is the framework's sum over the expand).  The graph count comes from the batch when it
+        carries one (no host sync: capturable), else from the one read-back `_num_graphs` does for the readouts."""
+        G = _num_graphs(batch, _get(data, "num_graphs"))
+        if batch.is_cuda and torch.is_grad_enabled() and self.training:
+            # (their launches are over G rows: the bf16-split route starts at 4096 of them, with splits of their own)
+            prepare_mlp_splits(list(self.mlp_virtualnode_list), G)
+        return self.virtualnode_embedding.weight.expand(G, -1)
 
-    def _vn_update(self, l, vn, h_in, batch):
-        tmp = global_add_pool(h_in, batch, vn.size(0)) + vn
-        upd = self.dropout(self.mlp_virtualnode_list[l](tmp))
+    def _vn_add(self, l, h, vn, batch):
+        """(h + vn[batch], global_add_pool(h + vn[batch]) + vn): one launch on the device (ops.virtual_node_add); the pooled
+        sum only for a layer that updates the virtual node."""
+        return virtual_node_add(h, vn, batch, vn.size(0), l < self.num_layer - 1)
+
+    def _vn_update(self, l, vn, tmp):
+        G = tmp.size(0)
+        if tmp.is_cuda:
+            # the MLP's launches are over G rows and static; a dynamic_rows capacity equal to G would hand them the live NODE count
+            refuse_dynamic_rows("the virtual-node MLP over as many graphs as the batch has node rows", G)
+        mlp = self.mlp_virtualnode_list[l]
+        # (one graph in training mode: the framework modules, whose BatchNorm1d raises as it does in the reference)
+        upd = self.dropout(mlp(tmp) if G == 1 and mlp[1].training else mlp_linear_bn_relu_x2(mlp, tmp))
         return vn + upd if self.residual else upd
 
     def _jk(self, h_list):
@@ -419,11 +437,11 @@ class GNN(_KHopBody):
         x = self._inputs(data)
         _prepare_splits(self.gnns, x)
         periph = self._peripheral(data, x.size(0), x)
-        vn = self._vn_init(batch, edge_index) if self.virtual_node else None
+        vn, vn_pool = (self._vn_init(data, batch), None) if self.virtual_node else (None, None)
         h_list = [x]
         for l in range(self.num_layer):
             if self.virtual_node:
-                h_list[l] = h_list[l] + vn[batch]
+                h_list[l], vn_pool = self._vn_add(l, h_list[l], vn, batch)
             # norm (+ residual) in one pass whenever no dropout mask sits between them (as in GNNPlus below)
             fuse_res = self.residual and (self.dropout.p == 0.0 or not self.training or l == self.num_layer - 1)
             # (this layer is the LAST of the state's readers to run backward - the norm's residual branch and the
@@ -439,7 +457,7 @@ class GNN(_KHopBody):
                 h = h + h_list[l]
             h_list.append(h)
             if self.virtual_node and l < self.num_layer - 1:
-                vn = self._vn_update(l, vn, h_list[l], batch)
+                vn = self._vn_update(l, vn, vn_pool)
         return self._jk(h_list)
 
 
@@ -471,11 +489,11 @@ class GNNPlus(_KHopBody):
         x = self._inputs(data)
         _prepare_splits(self.gnns, x)
         periph = self._peripheral(data, x.size(0), x)
-        vn = self._vn_init(batch, edge_index) if self.virtual_node else None
+        vn, vn_pool = (self._vn_init(data, batch), None) if self.virtual_node else (None, None)
         h_list, last_h = [x], x
         for l in range(self.num_layer):
             if self.virtual_node:
-                h_list[l] = h_list[l] + vn[batch]
+                h_list[l], vn_pool = self._vn_add(l, h_list[l], vn, batch)
             k = min(l + 1, self.K)
             slots = [h_list[l - m] for m in range(k)]                  # slot m = state of layer l-m
             pek = pe_attr[:, :k - 1] if pe_attr is not None else None
@@ -501,7 +519,7 @@ class GNNPlus(_KHopBody):
                 last_h = h
             h_list.append(h)
             if self.virtual_node and l < self.num_layer - 1:
-                vn = self._vn_update(l, vn, h_list[l], batch)
+                vn = self._vn_update(l, vn, vn_pool)
         return self._jk(h_list)
 
 
@@ -537,11 +555,11 @@ class GNNPrime(_KHopBody):
         x = self._inputs(data)
         _prepare_splits(list(self.khop_gnns) + list(self.gins), x)
         periph = self._peripheral(data, x.size(0), x)
-        vn = self._vn_init(batch, edge_index) if self.virtual_node else None
+        vn, vn_pool = (self._vn_init(data, batch), None) if self.virtual_node else (None, None)
         h_list = [x]
         for l in range(self.num_layer):
             if self.virtual_node:
-                h_list[l] = h_list[l] + vn[batch]
+                h_list[l], vn_pool = self._vn_add(l, h_list[l], vn, batch)
             layer = self.khop_gnns[l] if l < self.num_l1_layer else self.gins[l - self.num_l1_layer]
             if h_list[l].is_cuda:
                 h_list[l]._kp_last_reader = layer       # (as in GNN.forward: the norm's residual and the JK projection come later)
@@ -558,7 +576,7 @@ class GNNPrime(_KHopBody):
                 h = h + h_list[l]
             h_list.append(h)
             if self.virtual_node and l < self.num_layer - 1:
-                vn = self._vn_update(l, vn, h_list[l], batch)
+                vn = self._vn_update(l, vn, vn_pool)
         return self._jk(h_list)
 
 

@@ -1270,19 +1270,27 @@ def graph_ptr_of(batch, num_graphs):
     return ptr
 
 
+def _segment_pool_launch(x, ptr, num_graphs, mean=False):
+    """[G,D] sum / mean of the rows of x [N,D] per graph: one kpgnn_segment_pool_fwd launch."""
+    N, D = x.shape
+    if x.stride(1) != 1 or x.stride(0) < D:
+        x = x.contiguous()
+    out = torch.empty((num_graphs, D), dtype=torch.float32, device=x.device)
+    d = _lib.PoolDesc()
+    d.N, d.G, d.D, d.mode = N, num_graphs, D, 1 if mean else 0
+    d.n_dyn = dyn_ptr(N)
+    d.graph_ptr, d.x, d.x_stride, d.out = ptr.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr()
+    _lib.launch("kpgnn_segment_pool_fwd", x.device, ctypes.byref(d))
+    return out
+
+
 class SegmentPool(torch.autograd.Function):
     """out[g] = sum / mean of the rows of graph g (kpgnn_segment_pool_*): one launch per direction, no atomics."""
 
     @staticmethod
     def forward(ctx, x, batch, ptr, num_graphs, mean):
-        x = _last_contig(x)
         N, D = x.shape
-        out = torch.empty((num_graphs, D), dtype=torch.float32, device=x.device)
-        d = _lib.PoolDesc()
-        d.N, d.G, d.D, d.mode = N, num_graphs, D, 1 if mean else 0
-        d.n_dyn = dyn_ptr(N)
-        d.graph_ptr, d.x, d.x_stride, d.out = ptr.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr()
-        _lib.launch("kpgnn_segment_pool_fwd", x.device, ctypes.byref(d))
+        out = _segment_pool_launch(x, ptr, num_graphs, mean)
         ctx.save_for_backward(batch, ptr)
         ctx.dims = (N, D, num_graphs, mean)
         return out
@@ -1312,6 +1320,73 @@ def segment_pool(x, batch, num_graphs, mean=False):
             out = out / cnt.clamp(min=1).unsqueeze(-1)
         return out
     return SegmentPool.apply(x, batch.long() if batch.dtype != torch.int64 else batch, graph_ptr_of(batch, num_graphs), num_graphs, mean)
+
+
+# ------------------------------------------------------------------------------------------------ virtual node
+def _vn_launch(x, v, ptr, num_graphs, want_pool, out=None):
+    """(x + v[g], sum of that per graph + v or None) as one kpgnn_vn_add_pool launch; x [N,D], v [G,D] (row stride 0 allowed);
+    into `out` when given (a contiguous [N,D] fp32 tensor)."""
+    N, D = x.shape
+    if x.stride(1) != 1 or x.stride(0) < D:
+        x = x.contiguous()
+    if v.stride(1) != 1 or 0 < v.stride(0) < D:
+        v = v.contiguous()
+    if out is None:
+        out = torch.empty((N, D), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (N, D) and out.is_contiguous()
+    pooled = torch.empty((num_graphs, D), dtype=torch.float32, device=x.device) if want_pool else None
+    d = _lib.VnDesc()
+    d.N, d.G, d.D = N, num_graphs, D
+    d.n_dyn = dyn_ptr(N)
+    d.graph_ptr, d.x, d.x_stride, d.v, d.v_stride = ptr.data_ptr(), x.data_ptr(), x.stride(0), v.data_ptr(), v.stride(0)
+    d.out, d.out_stride, d.pooled = out.data_ptr(), D, _ptr(pooled)
+    _lib.launch("kpgnn_vn_add_pool", x.device, ctypes.byref(d))
+    return out, pooled
+
+
+class VirtualNodeAdd(torch.autograd.Function):
+    """out = x + vn[graph of the row], pooled = per-graph sum of out + vn (kpgnn_vn_add_pool): one launch per direction - the
+    backward (gx = gout + gpooled[g], gvn = per-graph sum of gx + gpooled) is the same kernel on the gradients.  Without
+    `pooled`, gx is gout itself and gvn one segmented sum."""
+
+    @staticmethod
+    def forward(ctx, x, vn, ptr, num_graphs, want_pool):
+        out, pooled = _vn_launch(x, vn, ptr, num_graphs, want_pool)
+        ctx.save_for_backward(ptr)
+        ctx.dims = (num_graphs, want_pool)
+        return out, pooled
+
+    @staticmethod
+    def backward(ctx, gout, gpooled):
+        ptr, = ctx.saved_tensors
+        G, want_pool = ctx.dims
+        if want_pool:
+            gx, gv = _vn_launch(gout, gpooled, ptr, G, True)
+            return gx, gv, None, None, None
+        gv = _segment_pool_launch(gout, ptr, G) if ctx.needs_input_grad[1] else None
+        return gout, gv, None, None, None
+
+
+def virtual_node_add(x, vn, batch, num_graphs, want_pool):
+    """The virtual node's two node-level steps (models/GNNs.py:196-199,227-230) for x [N,D] and the virtual-node rows vn [G,D]
+    (an expanded single row is read as such): returns (x + vn[batch], global_add_pool(x + vn[batch]) + vn or None).
+    fp32 device tensors up to D = 256 run kpgnn_vn_add_pool, driven by the graph pointer of `batch` (rows beyond its last
+    entry are left alone: safe on a dataset.StaticBatch); everything else keeps the framework expression."""
+    if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and vn.dtype == torch.float32 and x.shape[1] <= 256
+            and tuple(vn.shape) == (num_graphs, x.shape[1])):
+        if x.is_cuda:
+            refuse_dynamic_rows("the virtual node on the framework path", x.shape[0])
+        out = x + vn[batch]
+        if not want_pool:
+            return out, None
+        if out.is_cuda and out.dim() == 2 and out.dtype == torch.float32:
+            return out, segment_pool(out, batch, num_graphs) + vn
+        return out, out.new_zeros((num_graphs,) + tuple(out.shape[1:])).index_add_(0, batch, out) + vn
+    _require_cuda(vn, batch)
+    ptr = graph_ptr_of(batch, num_graphs)
+    if not torch.is_grad_enabled() or not (x.requires_grad or vn.requires_grad):
+        return _vn_launch(x, vn, ptr, num_graphs, want_pool)        # no autograd node, nothing saved
+    return VirtualNodeAdd.apply(x, vn, ptr, num_graphs, want_pool)
 
 
 class AttentionPool(torch.autograd.Function):
