@@ -1096,6 +1096,53 @@ size_t kpgnn_hop_mlp_workspace_bytes(int64_t N, int32_t K, int32_t DI, int32_t D
 int kpgnn_hop_mlp_fwd(const kpgnn_hop_mlp_desc* d, kpgnn_stream_t stream);
 int kpgnn_hop_mlp_bwd(const kpgnn_hop_mlp_desc* d, kpgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Dropout (+ residual) with counter-based masks (csrc/dropout.hip; models/GNNs.py, the self.dropout sites):
+ *   fwd:  out[n,c] = keep ? fmaf(x[n,c], scale, residual[n,c]) : residual[n,c]      (no residual: x * scale / 0)
+ *   bwd:  out[n,c] = keep ? x[n,c] * scale : 0         with x := dL/dout, out := dL/dx; the residual branch's gradient is
+ *         dL/dout itself and is nobody's launch
+ * Mask: the LOGICAL element e = n * C + c (int64: independent of strides and of the capacity N) is kept iff
+ *   word (e & 3) of Philox4x32-10(counter = (lo32(e >> 2), hi32(e >> 2), lo32(call), hi32(call)), key = (lo32(seed), hi32(seed)))
+ *   >= thr (unsigned), with the standard constants (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 /
+ *   0xBB67AE85).  The host forms thr = (uint32) min(4294967295, floor(p * 2^32)) and scale = (float)(1 / (1 - p)) in double.
+ * Call ids live on the device.  fwd reads (seed, calls) from `state`, uses `calls` as its call id, leaves that id in call_io
+ * and advances state[1] by one once every block has read it (the block that finishes last does it: `ticket` counts the
+ * arrivals and is zero again when the launch ends).  Nothing about the id travels through the arguments, so a replayed
+ * hipGraph draws a fresh mask on every replay.  bwd recomputes the mask from state[0] and call_io[0] and leaves state alone.
+ * Launches that share a `state` must be ordered on the device (one stream, or one captured graph without parallel branches
+ * through them).  Rows at or beyond *n_dyn are neither read nor written; N == 0 launches nothing and consumes no id.
+ * No limit on C: 16-byte accesses when C % 4 == 0, every stride is a multiple of 4 and every pointer is 16-byte aligned; a
+ * scalar path otherwise (one Philox call per element there: four times the arithmetic, correct but not tuned).  out may be x (or the residual) itself.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct kpgnn_dropout_desc {
+    int64_t N; int32_t C;                          /* rows (capacity with n_dyn), row width (>= 1) */
+    const float* x; int64_t x_stride;              /* device [N,C], row stride in floats (>= C) */
+    float* out; int64_t out_stride;                /* device [N,C] */
+    const float* residual; int64_t r_stride;       /* device [N,C] or NULL (fwd only; bwd ignores it) */
+    uint32_t thr; float scale;
+    int64_t* state;                                /* device int64[2]: seed, calls */
+    int64_t* call_io;                              /* device int64[1]: fwd writes its call id, bwd reads it */
+    int64_t* ticket;                               /* device int64[1] (fwd only): the arrival counter of the call-id advance.  The
+                                                    * caller zeroes it once; every completed launch leaves it zero again.  A launch
+                                                    * that was aborted leaves it non-zero: zero it again before the next one
+                                                    * (kp_gnn_amd.ops.dropout_seed does) */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= N; kpgnn_wgrad_desc explains); NULL: all N rows */
+} kpgnn_dropout_desc;
+
+int kpgnn_dropout_fwd(const kpgnn_dropout_desc* d, kpgnn_stream_t stream);
+int kpgnn_dropout_bwd(const kpgnn_dropout_desc* d, kpgnn_stream_t stream);
+
+/* The keep mask (1 = kept) of an explicit (seed, call) as uint8 [N,C] contiguous; consumes no call id.  The test and debug
+ * surface of the definition above. */
+typedef struct kpgnn_dropout_mask_desc {
+    int64_t seed, call;
+    int64_t N; int32_t C;
+    uint32_t thr;
+    uint8_t* mask;                                 /* device [N,C] */
+} kpgnn_dropout_mask_desc;
+
+int kpgnn_dropout_mask(const kpgnn_dropout_mask_desc* d, kpgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

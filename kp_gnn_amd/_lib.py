@@ -304,6 +304,20 @@ class VnDesc(ctypes.Structure):
     ]
 
 
+class DropoutDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("C", c_i32),
+        ("x", c_vp), ("x_stride", c_i64), ("out", c_vp), ("out_stride", c_i64), ("residual", c_vp), ("r_stride", c_i64),
+        ("thr", ctypes.c_uint32), ("scale", ctypes.c_float),
+        ("state", c_vp), ("call_io", c_vp), ("ticket", c_vp),
+        ("n_dyn", c_vp),
+    ]
+
+
+class DropoutMaskDesc(ctypes.Structure):
+    _fields_ = [("seed", c_i64), ("call", c_i64), ("N", c_i64), ("C", c_i32), ("thr", ctypes.c_uint32), ("mask", c_vp)]
+
+
 class AttnPoolDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i64), ("G", c_i32), ("D", c_i32),
@@ -409,6 +423,9 @@ SIGNATURES = {
     "kpgnn_segment_pool_fwd": (ctypes.c_int, [ctypes.POINTER(PoolDesc), c_vp]),
     "kpgnn_segment_pool_bwd": (ctypes.c_int, [ctypes.POINTER(PoolDesc), c_vp]),
     "kpgnn_vn_add_pool": (ctypes.c_int, [ctypes.POINTER(VnDesc), c_vp]),
+    "kpgnn_dropout_fwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
+    "kpgnn_dropout_bwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
+    "kpgnn_dropout_mask": (ctypes.c_int, [ctypes.POINTER(DropoutMaskDesc), c_vp]),
     "kpgnn_attn_pool_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "kpgnn_attn_pool_fwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),
     "kpgnn_attn_pool_bwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),

@@ -15,8 +15,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .layers.gine import GINEConv
-from .ops import (DictPeripheral, attention_pool, embedding_rows, enc_tables, refuse_dynamic_rows, segment_pool, table_gather_sum,
-                  virtual_node_add)
+from .ops import (DictPeripheral, attention_pool, dropout_add, embedding_rows, enc_tables, native_dropout_applies,
+                  refuse_dynamic_rows, segment_pool, table_gather_sum, virtual_node_add)
 from .ops_dense import (JKConcatLinear, batch_norm_act, head_linear, jk_concat_linear_nograd, mlp_linear_bn_relu_x2,
                         prepare_mlp_splits, score_head)
 
@@ -375,6 +375,15 @@ class _KHopBody(nn.Module):
         sum only for a layer that updates the virtual node."""
         return virtual_node_add(h, vn, batch, vn.size(0), l < self.num_layer - 1)
 
+    def _drop(self, h, residual=None, module=None):
+        """module(h) (+ residual), module = self.dropout unless given: one launch with counter-based masks where the native
+        route applies (ops.dropout_add: fp32 device rows, training mode, 0 < p < 1), else the framework module and add."""
+        module = self.dropout if module is None else module
+        if native_dropout_applies(h, module.p, module.training):
+            return dropout_add(h, module.p, True, residual)
+        h = module(h)
+        return h if residual is None else h + residual
+
     def _vn_update(self, l, vn, tmp):
         G = tmp.size(0)
         if tmp.is_cuda:
@@ -382,19 +391,22 @@ class _KHopBody(nn.Module):
             refuse_dynamic_rows("the virtual-node MLP over as many graphs as the batch has node rows", G)
         mlp = self.mlp_virtualnode_list[l]
         # (one graph in training mode: the framework modules, whose BatchNorm1d raises as it does in the reference)
-        upd = self.dropout(mlp(tmp) if G == 1 and mlp[1].training else mlp_linear_bn_relu_x2(mlp, tmp))
+        upd = mlp(tmp) if G == 1 and mlp[1].training else mlp_linear_bn_relu_x2(mlp, tmp)
+        if self.residual and native_dropout_applies(upd, self.dropout.p, self.dropout.training):
+            return self._drop(upd, vn)           # (the residual rides in the dropout launch)
+        upd = self._drop(upd)
         return vn + upd if self.residual else upd
 
     def _jk(self, h_list):
         if self.JK == "concat" and h_list[0].is_cuda and h_list[0].dtype == torch.float32 and torch.is_grad_enabled():
             lin = self.output_proj[0]
-            return self.output_proj[2](JKConcatLinear.apply(lin.weight, lin.bias, *h_list))
+            return self._drop(JKConcatLinear.apply(lin.weight, lin.bias, *h_list), module=self.output_proj[2])
         if self.JK == "concat" and h_list[0].is_cuda and h_list[0].dtype == torch.float32:
             # no grad (evaluation): the grouped-K kernel directly - no autograd node, nothing saved
             lin = self.output_proj[0]
             y = jk_concat_linear_nograd(lin.weight, lin.bias, h_list)
             if y is not None:
-                return self.output_proj[2](y)
+                return self._drop(y, module=self.output_proj[2])
         if self.JK == "concat":
             rep = torch.cat(h_list, dim=1)
         elif self.JK == "last":
@@ -410,6 +422,8 @@ class _KHopBody(nn.Module):
             rep = (hs * torch.softmax(score.sum(-1), dim=1).unsqueeze(-1)).sum(1)
         else:
             raise NameError(f"JK={self.JK} is not implemented (as in the reference, Q14)")
+        if native_dropout_applies(rep, self.output_proj[2].p, self.output_proj[2].training):
+            return self._drop(self.output_proj[1](self.output_proj[0](rep)), module=self.output_proj[2])
         return self.output_proj(rep)
 
 
@@ -451,10 +465,11 @@ class GNN(_KHopBody):
                 h_list[l]._kp_last_reader = self.gnns[l]
             h = self.norms[l](self.gnns[l](h_list[l], edge_index, edge_attr, pe_attr, periph),
                               residual=h_list[l] if fuse_res else None)
+            res = h_list[l] if self.residual and not fuse_res else None
             if l != self.num_layer - 1:
-                h = self.dropout(h)
-            if self.residual and not fuse_res:
-                h = h + h_list[l]
+                h = self._drop(h, res)           # (with a mask between norm and residual, the add rides in the dropout launch)
+            elif res is not None:
+                h = h + res
             h_list.append(h)
             if self.virtual_node and l < self.num_layer - 1:
                 vn = self._vn_update(l, vn, vn_pool)
@@ -511,11 +526,12 @@ class GNNPlus(_KHopBody):
             else:
                 h = self.gnns[l](torch.stack(slots, dim=1), edge_index, edge_attr[:, :k], pek, periph[:, :k])
                 h = self.norms[l](h, residual=res)   # norm (+ residual) in one pass
+            res = last_h if self.residual and not fuse_res else None
             if l != self.num_layer - 1:
-                h = self.dropout(h)
+                h = self._drop(h, res)
+            elif res is not None:
+                h = h + res
             if self.residual:
-                if not fuse_res:
-                    h = h + last_h
                 last_h = h
             h_list.append(h)
             if self.virtual_node and l < self.num_layer - 1:
@@ -570,10 +586,11 @@ class GNNPrime(_KHopBody):
             drops = l < self.num_l1_layer or l != self.num_layer - 1   # (:659 drops out after every K-hop layer)
             fuse_res = self.residual and (self.dropout.p == 0.0 or not self.training or not drops)
             h = self.norms[l](h, residual=h_list[l] if fuse_res else None)
+            res = h_list[l] if self.residual and not fuse_res else None
             if drops:
-                h = self.dropout(h)
-            if self.residual and not fuse_res:
-                h = h + h_list[l]
+                h = self._drop(h, res)
+            elif res is not None:
+                h = h + res
             h_list.append(h)
             if self.virtual_node and l < self.num_layer - 1:
                 vn = self._vn_update(l, vn, vn_pool)

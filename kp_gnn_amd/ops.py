@@ -1389,6 +1389,143 @@ def virtual_node_add(x, vn, batch, num_graphs, want_pool):
     return VirtualNodeAdd.apply(x, vn, ptr, num_graphs, want_pool)
 
 
+# ------------------------------------------------------------------------------------------------ dropout (+ residual)
+# Masks are a function of (seed, call id, row, column, width) alone (kpgnn.h, kpgnn_dropout_desc): Philox4x32-10 keyed by the
+# seed, counted by the logical element and the ordinal of the launch since seeding.  Seed and ordinal live in a per-device
+# int64[3] tensor {seed, calls, ticket}; the forward kernel advances `calls` itself, so a replayed graph draws fresh masks, and
+# the backward recomputes the mask from the int64[1] cell the forward left its call id in - nothing of [N,C] size is saved.
+_NATIVE_DROPOUT = False    # opt-in: a captured step is slower with it than with nn.Dropout as measured
+_DROP_STATE = {}      # device index -> int64[3] device tensor
+
+
+def set_native_dropout(on):
+    """Route training-mode dropout of fp32 device rows through kpgnn_dropout_* (True) or keep nn.Dropout (False, the default).
+    Returns the previous setting."""
+    global _NATIVE_DROPOUT
+    prev, _NATIVE_DROPOUT = _NATIVE_DROPOUT, bool(on)
+    return prev
+
+
+def native_dropout():
+    return _NATIVE_DROPOUT
+
+
+def _drop_device(device):
+    device = torch.device("cuda" if device is None else device)
+    return torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
+
+
+def _signed64(v):
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def dropout_seed(seed, device=None):
+    """(seed, 0) into the device's dropout state: the next dropout launch has call id 0.  Data-parallel callers seed every
+    rank differently: dropout_seed(seed + rank)."""
+    device = _drop_device(device)
+    host = torch.tensor([_signed64(seed), 0, 0], dtype=torch.int64)
+    st = _DROP_STATE.get(device.index)
+    if st is None:
+        _DROP_STATE[device.index] = host.to(device)
+    else:
+        st.copy_(host)
+
+
+def dropout_state(device=None):
+    """The device's int64[3] {seed, calls, ticket}; a state never seeded starts from torch.initial_seed() at its first use.
+    That first use copies from the host: it cannot happen inside a stream capture (KpgnnError) - call dropout_seed, or run one
+    eager step, before capturing."""
+    device = _drop_device(device)
+    if device.index not in _DROP_STATE:
+        if torch.cuda.is_current_stream_capturing():
+            # (creating it is a host-to-device copy and an allocation outside the graph's pool)
+            raise _lib.KpgnnError("the dropout state of this device does not exist yet and cannot be created inside a stream "
+                                  "capture: call ops.dropout_seed(seed) (or run one eager step) before capturing")
+        dropout_seed(torch.initial_seed(), device)
+    return _DROP_STATE[device.index]
+
+
+def dropout_params(p):
+    """(thr, scale) of the mask definition, formed in double: keep iff word >= thr; kept values are multiplied by scale."""
+    p = float(p)
+    return min(4294967295, int(p * 4294967296.0)), 1.0 / (1.0 - p)
+
+
+def dropout_mask(shape, p, seed, call, device):
+    """The keep mask (bool [N,C]) of launch `call` under `seed` for rows of width C: kpgnn_dropout_mask, no call id consumed."""
+    N, C = (int(s) for s in shape)
+    mask = torch.empty((N, C), dtype=torch.uint8, device=device)
+    _require_cuda(mask)
+    d = _lib.DropoutMaskDesc()
+    d.seed, d.call, d.N, d.C, d.thr, d.mask = _signed64(seed), _signed64(call), N, C, dropout_params(p)[0], mask.data_ptr()
+    if N:
+        _lib.launch("kpgnn_dropout_mask", mask.device, ctypes.byref(d))
+    return mask.view(torch.bool)
+
+
+def _rows_view(t, C):
+    """[N,C] fp32 rows the kernels can walk: unit column stride, rows that do not overlap (a column slice stays a view)."""
+    return t if t.stride(1) == 1 and t.stride(0) >= C else t.contiguous()
+
+
+def _dropout_launch(name, x, residual, cell, p):
+    N, C = x.shape
+    x = _rows_view(x, C)
+    out = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    state = dropout_state(x.device)
+    d = _lib.DropoutDesc()
+    d.N, d.C = N, C
+    d.x, d.x_stride, d.out, d.out_stride = x.data_ptr(), x.stride(0), out.data_ptr(), C
+    if residual is not None:
+        residual = _rows_view(residual, C)
+        d.residual, d.r_stride = residual.data_ptr(), residual.stride(0)
+    d.thr, d.scale = dropout_params(p)
+    d.state, d.call_io, d.ticket = state.data_ptr(), cell.data_ptr(), state.data_ptr() + 16
+    d.n_dyn = dyn_ptr(N)
+    _lib.launch(name, x.device, ctypes.byref(d))
+    return out
+
+
+class DropoutAdd(torch.autograd.Function):
+    """out = dropout(x, p) (+ residual) as one kpgnn_dropout_fwd launch; the backward is one kpgnn_dropout_bwd launch that
+    recomputes the mask from the saved int64[1] call cell, and the residual's gradient is the incoming one itself."""
+
+    @staticmethod
+    def forward(ctx, x, residual, p):
+        cell = torch.empty(1, dtype=torch.int64, device=x.device)
+        out = _dropout_launch("kpgnn_dropout_fwd", x, residual, cell, p)
+        ctx.save_for_backward(cell)
+        ctx.p = p
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        cell, = ctx.saved_tensors
+        gx = _dropout_launch("kpgnn_dropout_bwd", gout, None, cell, ctx.p) if ctx.needs_input_grad[0] else None
+        return gx, (gout if ctx.needs_input_grad[1] else None), None
+
+
+def native_dropout_applies(x, p, training):
+    return bool(_NATIVE_DROPOUT and training and 0.0 < p < 1.0 and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
+                and x.numel() > 0)
+
+
+def dropout_add(x, p, training, residual=None):
+    """F.dropout(x, p, training) (+ residual).  fp32 device rows [N,C] in training mode with 0 < p < 1 run kpgnn_dropout_fwd
+    (masks: the counter-based generator above, not the framework's; rows beyond the live count of a dynamic_rows block are left
+    alone); everything else - evaluation, p == 0, p == 1, other dtypes, CPU tensors, the switch off (set_native_dropout, off by default) - keeps the
+    framework expression."""
+    if not native_dropout_applies(x, p, training) or (
+            residual is not None and not (residual.is_cuda and residual.dtype == torch.float32 and residual.shape == x.shape)):
+        out = torch.nn.functional.dropout(x, p, training)
+        return out if residual is None else out + residual
+    if not torch.is_grad_enabled() or not (x.requires_grad or (residual is not None and residual.requires_grad)):
+        cell = torch.empty(1, dtype=torch.int64, device=x.device)
+        return _dropout_launch("kpgnn_dropout_fwd", x, residual, cell, p)      # no autograd node, nothing saved
+    return DropoutAdd.apply(x, residual, float(p))
+
+
 class AttentionPool(torch.autograd.Function):
     """PyG's AttentionalAggregation(gate_nn=nn.Linear(D, 1)) over the node ranges of a collated batch (kpgnn_attn_pool_*):
     one launch forward, one plus a fixed-order reduce backward, no atomics."""
