@@ -1143,6 +1143,46 @@ typedef struct kpgnn_dropout_mask_desc {
 
 int kpgnn_dropout_mask(const kpgnn_dropout_mask_desc* d, kpgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Jumping-knowledge reduce over the S = num_layer + 1 states of a body (csrc/jk_reduce.hip; models/GNNs.py, the JK branches
+ * "sum", "max" and the weighted sum of "attention").  The states are S separate [N,H] tensors read IN PLACE through a pointer
+ * table: nothing of [S,N,H] size is formed in the forward.  All fp32.
+ *   KPGNN_JK_SUM      out[n,c] = x[0][n,c] + x[1][n,c] + ... + x[S-1][n,c], added in slot order (deterministic, independent of
+ *                     the launch geometry).  No backward entry: every state's gradient is dL/dout itself.
+ *   KPGNN_JK_MAX      out[n,c] = max_l x[l][n,c].  Slots are walked upwards and compared with `>`: among equal values (+0 and -0
+ *                     are equal) the LOWEST slot wins, and arg[n,c] records the winner.  A NaN in any slot gives NaN, as
+ *                     torch.max does; which slot arg then names is unspecified.
+ *                     bwd: gx[l][n,c] = arg[n,c] == l ? gout[n,c] : 0 - every live element of all S blocks is written.
+ *   KPGNN_JK_SOFTMAX  w[n,:] = softmax_l(score[n,:]) (max-subtracted), out[n,c] = sum_l w[n,l] x[l][n,c] in slot order.
+ *                     bwd: gx[l][n,c] = w[n,l] gout[n,c];  gscore[n,l] = w[n,l] (d_l - sum_m w[n,m] d_m) with
+ *                     d_l = <gout[n,:], x[l][n,:]>, summed per lane over its columns and then across the row's lanes (fixed
+ *                     order: a function of H alone).
+ * arg / w are written by fwd when given (they may be NULL when no backward follows) and read by bwd, which needs them.
+ * Rows at or beyond *n_dyn are neither read nor written, in either direction and in every output; N == 0 launches nothing.
+ * No limit on H: 16-byte accesses when H % 4 == 0, every stride is a multiple of 4 and every pointer is 16-byte aligned (arg:
+ * 4-byte); a scalar path otherwise.
+ * ---------------------------------------------------------------------------------------------- */
+#define KPGNN_JK_MAX_STATES 32
+enum { KPGNN_JK_SUM = 0, KPGNN_JK_MAX = 1, KPGNN_JK_SOFTMAX = 2 };
+
+typedef struct kpgnn_jk_desc {
+    int64_t N; int32_t H, S, mode;                 /* rows (capacity with n_dyn), row width (>= 1), states (1 .. 32), KPGNN_JK_* */
+    const float* x[KPGNN_JK_MAX_STATES];           /* device [N,H] each; entries l < S (fwd; bwd: SOFTMAX only) */
+    int64_t x_stride;                              /* the one row stride of every state, in floats (>= H) */
+    const float* score;                            /* device [N,S] contiguous (SOFTMAX fwd) */
+    float* out; int64_t out_stride;                /* device [N,H] (fwd) */
+    uint8_t* arg;                                  /* device uint8 [N,H] contiguous: the winning slot (MAX; fwd: optional out, bwd: in) */
+    float* w;                                      /* device [N,S] contiguous: the softmax weights (SOFTMAX; fwd: optional out, bwd: in) */
+    /* backward only */
+    const float* gout; int64_t gout_stride;        /* device [N,H] */
+    float* gx;                                     /* device [S,N,H] contiguous: block l is state l's gradient */
+    float* gscore;                                 /* device [N,S] contiguous (SOFTMAX) */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= N; kpgnn_wgrad_desc explains); NULL: all N rows */
+} kpgnn_jk_desc;
+
+int kpgnn_jk_reduce_fwd(const kpgnn_jk_desc* d, kpgnn_stream_t stream);
+int kpgnn_jk_reduce_bwd(const kpgnn_jk_desc* d, kpgnn_stream_t stream);     /* MAX and SOFTMAX; SUM is KPGNN_EINVAL */
+
 #ifdef __cplusplus
 }
 #endif

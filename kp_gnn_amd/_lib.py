@@ -318,6 +318,20 @@ class DropoutMaskDesc(ctypes.Structure):
     _fields_ = [("seed", c_i64), ("call", c_i64), ("N", c_i64), ("C", c_i32), ("thr", ctypes.c_uint32), ("mask", c_vp)]
 
 
+JK_SUM, JK_MAX, JK_SOFTMAX = 0, 1, 2     # include/kpgnn.h KPGNN_JK_*
+JK_MAX_STATES = 32
+
+
+class JkDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("H", c_i32), ("S", c_i32), ("mode", c_i32),
+        ("x", c_vp * JK_MAX_STATES), ("x_stride", c_i64), ("score", c_vp),
+        ("out", c_vp), ("out_stride", c_i64), ("arg", c_vp), ("w", c_vp),
+        ("gout", c_vp), ("gout_stride", c_i64), ("gx", c_vp), ("gscore", c_vp),
+        ("n_dyn", c_vp),
+    ]
+
+
 class AttnPoolDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i64), ("G", c_i32), ("D", c_i32),
@@ -426,6 +440,8 @@ SIGNATURES = {
     "kpgnn_dropout_fwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
     "kpgnn_dropout_bwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
     "kpgnn_dropout_mask": (ctypes.c_int, [ctypes.POINTER(DropoutMaskDesc), c_vp]),
+    "kpgnn_jk_reduce_fwd": (ctypes.c_int, [ctypes.POINTER(JkDesc), c_vp]),
+    "kpgnn_jk_reduce_bwd": (ctypes.c_int, [ctypes.POINTER(JkDesc), c_vp]),
     "kpgnn_attn_pool_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "kpgnn_attn_pool_fwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),
     "kpgnn_attn_pool_bwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),

@@ -15,8 +15,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .layers.gine import GINEConv
-from .ops import (DictPeripheral, attention_pool, dropout_add, embedding_rows, enc_tables, native_dropout_applies,
-                  refuse_dynamic_rows, segment_pool, table_gather_sum, virtual_node_add)
+from .ops import (DictPeripheral, attention_pool, dropout_add, embedding_rows, enc_tables, jk_native_applies, jk_reduce,
+                  native_dropout_applies, refuse_dynamic_rows, segment_pool, table_gather_sum, virtual_node_add)
 from .ops_dense import (JKConcatLinear, batch_norm_act, head_linear, jk_concat_linear_nograd, mlp_linear_bn_relu_x2,
                         prepare_mlp_splits, score_head)
 
@@ -412,14 +412,19 @@ class _KHopBody(nn.Module):
         elif self.JK == "last":
             rep = h_list[-1]
         elif self.JK == "max":
-            rep = torch.stack(h_list, dim=-1).max(dim=-1).values
+            # (fp32 device states: one kpgnn_jk_reduce_fwd launch over the states in place, ops.jk_reduce; else the stack)
+            rep = jk_reduce(h_list, "max") if jk_native_applies(h_list, "max") else torch.stack(h_list, dim=-1).max(dim=-1).values
         elif self.JK == "sum":
-            rep = torch.stack(h_list, dim=0).sum(dim=0)
+            rep = jk_reduce(h_list, "sum") if jk_native_applies(h_list, "sum") else torch.stack(h_list, dim=0).sum(dim=0)
         elif self.JK == "attention":
+            # the scoring LSTM keeps its framework module and its stacked input; the weighted sum reads the states in place
             hs = torch.stack(h_list, dim=1)
             self.attention_lstm.flatten_parameters()
             score, _ = self.attention_lstm(hs)
-            rep = (hs * torch.softmax(score.sum(-1), dim=1).unsqueeze(-1)).sum(1)
+            if jk_native_applies(h_list, "softmax"):
+                rep = jk_reduce(h_list, "softmax", score.sum(-1))
+            else:
+                rep = (hs * torch.softmax(score.sum(-1), dim=1).unsqueeze(-1)).sum(1)
         else:
             raise NameError(f"JK={self.JK} is not implemented (as in the reference, Q14)")
         if native_dropout_applies(rep, self.output_proj[2].p, self.output_proj[2].training):

@@ -1526,6 +1526,171 @@ def dropout_add(x, p, training, residual=None):
     return DropoutAdd.apply(x, residual, float(p))
 
 
+# ------------------------------------------------------------------------------------------------ jumping-knowledge reduce
+# sum / max / softmax-weighted sum over the S = num_layer + 1 states of a body (kpgnn.h, kpgnn_jk_desc): the states are read in
+# place through a pointer table, so nothing of [S,N,H] size is formed in the forward; max saves a uint8 [N,H] winner slot, softmax
+# its [N,S] weights (and references to the states, which are alive anyway).
+JK_MODES = {"sum": _lib.JK_SUM, "max": _lib.JK_MAX, "softmax": _lib.JK_SOFTMAX}
+_NATIVE_JK = {"sum": True, "max": True, "softmax": True}
+
+
+def set_native_jk(on, mode=None):
+    """Route the jumping-knowledge reduce of fp32 device states through kpgnn_jk_reduce_* (True, the default) or keep the
+    torch.stack expressions (False); for one mode ("sum", "max", "softmax") or, with mode=None, for all three.  Returns the
+    previous setting (native_jk(mode))."""
+    prev = native_jk(mode)
+    for m in (JK_MODES if mode is None else (mode,)):
+        if m not in JK_MODES:
+            raise ValueError(f"jumping-knowledge mode must be one of {sorted(JK_MODES)}, got {m!r}")
+        _NATIVE_JK[m] = bool(on)
+    return prev
+
+
+def native_jk(mode=None):
+    return all(_NATIVE_JK.values()) if mode is None else _NATIVE_JK[mode]
+
+
+def jk_native_applies(states, mode=None):
+    """Every state a CUDA fp32 2-D tensor of one (non-empty) shape [N,H], 1 <= S <= 32, and the native route switched on."""
+    S = len(states)
+    if not (native_jk(mode) and 1 <= S <= _lib.JK_MAX_STATES):
+        return False
+    shape = states[0].shape
+    return bool(all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape == shape for t in states)
+                and states[0].numel() > 0)
+
+
+def _jk_desc(states, mode):
+    N, H = states[0].shape
+    d = _lib.JkDesc()
+    d.N, d.H, d.S, d.mode = N, H, len(states), JK_MODES[mode]
+    for l, t in enumerate(states):
+        d.x[l] = t.data_ptr()
+    d.x_stride = H
+    d.n_dyn = dyn_ptr(N)
+    return d
+
+
+def _jk_fwd_launch(states, mode, score, save):
+    """(out, arg or w or None): one kpgnn_jk_reduce_fwd launch over contiguous states; arg / w only with `save`."""
+    N, H = states[0].shape
+    dev = states[0].device
+    out = torch.empty((N, H), dtype=torch.float32, device=dev)
+    d = _jk_desc(states, mode)
+    d.out, d.out_stride = out.data_ptr(), H
+    kept = None
+    if mode == "softmax":
+        d.score = score.data_ptr()
+        if save:
+            kept = torch.empty((N, len(states)), dtype=torch.float32, device=dev)
+            d.w = kept.data_ptr()
+    elif mode == "max" and save:
+        kept = torch.empty((N, H), dtype=torch.uint8, device=dev)
+        d.arg = kept.data_ptr()
+    _lib.launch("kpgnn_jk_reduce_fwd", dev, ctypes.byref(d))
+    return out, kept
+
+
+def _jk_bwd_launch(states, S, mode, kept, gout):
+    """(gx [S,N,H], gscore [N,S] or None): one kpgnn_jk_reduce_bwd launch (max: `states` is only asked for its shape)."""
+    N, H = gout.shape
+    dev = gout.device
+    gout = _rows_view(gout, H)
+    gx = torch.empty((S, N, H), dtype=torch.float32, device=dev)
+    if mode == "softmax":
+        d = _jk_desc(states, mode)
+        gscore = torch.empty((N, S), dtype=torch.float32, device=dev)
+        d.w, d.gscore = kept.data_ptr(), gscore.data_ptr()
+    else:
+        d = _lib.JkDesc()
+        d.N, d.H, d.S, d.mode, d.n_dyn = N, H, S, JK_MODES[mode], dyn_ptr(N)
+        gscore = None
+        d.arg = kept.data_ptr()
+    d.gout, d.gout_stride, d.gx = gout.data_ptr(), gout.stride(0), gx.data_ptr()
+    _lib.launch("kpgnn_jk_reduce_bwd", dev, ctypes.byref(d))
+    return gx, gscore
+
+
+class JKSum(torch.autograd.Function):
+    """out = sum of the states in slot order (kpgnn_jk_reduce_fwd); every state's gradient is the incoming one itself."""
+
+    @staticmethod
+    def forward(ctx, *states):
+        return _jk_fwd_launch(states, "sum", None, False)[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        return tuple(gout if need else None for need in ctx.needs_input_grad)
+
+
+class JKMax(torch.autograd.Function):
+    """out = elementwise max over the states, the lowest slot winning a tie; saves the uint8 [N,H] winner slot, and the
+    backward (one kpgnn_jk_reduce_bwd launch) routes gout to that slot's block of one [S,N,H] buffer, returned as views."""
+
+    @staticmethod
+    def forward(ctx, *states):
+        out, arg = _jk_fwd_launch(states, "max", None, True)
+        ctx.save_for_backward(arg)
+        ctx.S = len(states)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        arg, = ctx.saved_tensors
+        gx, _ = _jk_bwd_launch(None, ctx.S, "max", arg, gout)
+        return tuple(gx[l] if need else None for l, need in enumerate(ctx.needs_input_grad))
+
+
+class JKSoftmax(torch.autograd.Function):
+    """out = sum_l softmax(score)[n,l] * states[l][n,:]; saves the [N,S] weights and references to the states; the backward is
+    one kpgnn_jk_reduce_bwd launch for every state's gradient (views of one [S,N,H] buffer) and the score's."""
+
+    @staticmethod
+    def forward(ctx, score, *states):
+        out, w = _jk_fwd_launch(states, "softmax", score, True)
+        ctx.save_for_backward(w, *states)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        w, *states = ctx.saved_tensors
+        gx, gscore = _jk_bwd_launch(states, len(states), "softmax", w, gout)
+        return (gscore if ctx.needs_input_grad[0] else None,) + tuple(
+            gx[l] if need else None for l, need in enumerate(ctx.needs_input_grad[1:]))
+
+
+def jk_reduce(states, mode, score=None):
+    """The jumping-knowledge reduce of models/GNNs.py over the list of states [N,H]: mode "sum", "max", or "softmax" with
+    score [N,S] (the weighted sum of JK attention: sum_l softmax(score)[:,l,None] * states[l]).  Where jk_native_applies, one
+    kpgnn_jk_reduce_fwd launch (rows beyond the live count of a dynamic_rows block are left alone) and, for max and softmax,
+    one kpgnn_jk_reduce_bwd launch; everything else - CPU tensors, other dtypes, S > 32, the switch off (set_native_jk) - keeps
+    the torch.stack expressions."""
+    if mode not in JK_MODES:
+        raise ValueError(f"jumping-knowledge mode must be one of {sorted(JK_MODES)}, got {mode!r}")
+    if (mode == "softmax") != (score is not None):
+        raise ValueError("jk_reduce: a score goes with mode 'softmax' and with no other")
+    states = list(states)
+    native = jk_native_applies(states, mode)
+    if native and score is not None:
+        native = score.is_cuda and score.dtype == torch.float32 and tuple(score.shape) == (states[0].shape[0], len(states))
+    if not native:
+        if mode == "max":
+            return torch.stack(states, dim=-1).max(dim=-1).values
+        if mode == "sum":
+            return torch.stack(states, dim=0).sum(dim=0)
+        return (torch.stack(states, dim=1) * torch.softmax(score, dim=1).unsqueeze(-1)).sum(1)
+    states = [t if t.is_contiguous() else t.contiguous() for t in states]
+    if score is not None:
+        score = score.contiguous()
+    if not torch.is_grad_enabled() or not any(t.requires_grad for t in states + ([] if score is None else [score])):
+        return _jk_fwd_launch([t.detach() for t in states], mode, score, False)[0]     # no autograd node, nothing saved
+    if mode == "sum":
+        return JKSum.apply(*states)
+    if mode == "max":
+        return JKMax.apply(*states)
+    return JKSoftmax.apply(score, *states)
+
+
 class AttentionPool(torch.autograd.Function):
     """PyG's AttentionalAggregation(gate_nn=nn.Linear(D, 1)) over the node ranges of a collated batch (kpgnn_attn_pool_*):
     one launch forward, one plus a fixed-order reduce backward, no atomics."""
