@@ -1183,6 +1183,48 @@ typedef struct kpgnn_jk_desc {
 int kpgnn_jk_reduce_fwd(const kpgnn_jk_desc* d, kpgnn_stream_t stream);
 int kpgnn_jk_reduce_bwd(const kpgnn_jk_desc* d, kpgnn_stream_t stream);     /* MAX and SOFTMAX; SUM is KPGNN_EINVAL */
 
+/* ------------------------------------------------------------------------------------------------
+ * The scoring LSTM of the attention jumping-knowledge readout (csrc/jk_lstm.hip; models/GNNs.py, the JK == "attention"
+ * branches): nn.LSTM(H, P, bidirectional=True) over the S states, summed over its 2P outputs.  With x[l] the S states [N,H]:
+ *   for dir in {forward, reverse}, t walked 0..S-1 (forward) or S-1..0 (reverse), h = c = 0 at the start:
+ *       (i,f,g,o) = W_ih[dir] x[t][n,:] + b_ih[dir] + W_hh[dir] h + b_hh[dir]       (torch's gate order: rows q, P+q, 2P+q, 3P+q)
+ *       c = sigmoid(f) c + sigmoid(i) tanh(g);   h = sigmoid(o) tanh(c)
+ *   score[n,t] = sum_q h_fwd[n,t,q] + sum_q h_rev[n,t,q]
+ * which is what kpgnn_jk_reduce_* consumes as `score` in mode KPGNN_JK_SOFTMAX.  The states are read in place through the
+ * pointer table (nothing of [N,S,H] size is formed in the forward); the input projection - 8P gate columns, both directions
+ * side by side, over N*S rows of H - runs on the fp32 matrix instruction, the recurrence and its BPTT one thread per
+ * (node, direction) with the state in registers.  All fp32, no atomics: the parameter gradients are per-tile partial sums
+ * over FIXED ranges of 64 rows added in tile order, so the same live rows give the same bits at any capacity N.
+ *   fwd: writes score; with `saved` != NULL also what bwd needs (kpgnn_jk_lstm_saved_bytes), in the kernels' own layout.
+ *        saved == NULL is the evaluation forward: nothing is kept (the pre-activations then pass through the workspace).
+ *   bwd: reads saved, gscore, the states and the weights; overwrites gx (block l = state l's gradient; NULL: skipped) and
+ *        dw_ih / dw_hh / db (db is the gradient of b_ih and of b_hh alike).
+ * Both need `workspace` of kpgnn_jk_lstm_workspace_bytes (16-byte aligned, as is saved).  Rows at or beyond *n_dyn are
+ * neither read nor written in any per-row output and contribute nothing to the parameter gradients (skipped, not multiplied
+ * by zero).  Limits: 1 <= P <= 16, 1 <= S <= 32, 1 <= H <= 256 (KPGNN_ELIMIT above, KPGNN_EINVAL below); N == 0 launches nothing.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct kpgnn_jk_lstm_desc {
+    int64_t N; int32_t H, P, S;                    /* rows (capacity with n_dyn), row width, LSTM hidden size, states */
+    const float* x[KPGNN_JK_MAX_STATES];           /* device [N,H] each; entries l < S */
+    int64_t x_stride;                              /* the one row stride of every state, in floats (>= H) */
+    const float* w_ih[2]; const float* w_hh[2];    /* device [4P,H], [4P,P]; index 0 = forward, 1 = reverse (nn.LSTM's own) */
+    const float* b_ih[2]; const float* b_hh[2];    /* device [4P] (fwd only) */
+    float* score;                                  /* device [N,S] contiguous (fwd) */
+    void* saved;                                   /* device, kpgnn_jk_lstm_saved_bytes: fwd optional out, bwd in */
+    /* backward only */
+    const float* gscore;                           /* device [N,S] contiguous */
+    float* gx;                                     /* device [S,N,H] contiguous or NULL */
+    float* dw_ih[2]; float* dw_hh[2]; float* db[2];/* device [4P,H], [4P,P], [4P] */
+    void* workspace; size_t workspace_bytes;       /* >= kpgnn_jk_lstm_workspace_bytes(N, H, P, S) */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= N; kpgnn_wgrad_desc explains); NULL: all N rows */
+} kpgnn_jk_lstm_desc;
+
+/* 0 = the shape is not covered. */
+size_t kpgnn_jk_lstm_saved_bytes(int64_t N, int32_t H, int32_t P, int32_t S);
+size_t kpgnn_jk_lstm_workspace_bytes(int64_t N, int32_t H, int32_t P, int32_t S);
+int kpgnn_jk_lstm_fwd(const kpgnn_jk_lstm_desc* d, kpgnn_stream_t stream);
+int kpgnn_jk_lstm_bwd(const kpgnn_jk_lstm_desc* d, kpgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -332,6 +332,21 @@ class JkDesc(ctypes.Structure):
     ]
 
 
+class JkLstmDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("H", c_i32), ("P", c_i32), ("S", c_i32),
+        ("x", c_vp * JK_MAX_STATES), ("x_stride", c_i64),
+        ("w_ih", c_vp * 2), ("w_hh", c_vp * 2), ("b_ih", c_vp * 2), ("b_hh", c_vp * 2),
+        ("score", c_vp), ("saved", c_vp),
+        ("gscore", c_vp), ("gx", c_vp), ("dw_ih", c_vp * 2), ("dw_hh", c_vp * 2), ("db", c_vp * 2),
+        ("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t),
+        ("n_dyn", c_vp),
+    ]
+
+
+JK_LSTM_MAX_P, JK_LSTM_MAX_H = 16, 256    # csrc/jk_lstm.hip kMaxP, kMaxH (S: JK_MAX_STATES)
+
+
 class AttnPoolDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i64), ("G", c_i32), ("D", c_i32),
@@ -442,6 +457,10 @@ SIGNATURES = {
     "kpgnn_dropout_mask": (ctypes.c_int, [ctypes.POINTER(DropoutMaskDesc), c_vp]),
     "kpgnn_jk_reduce_fwd": (ctypes.c_int, [ctypes.POINTER(JkDesc), c_vp]),
     "kpgnn_jk_reduce_bwd": (ctypes.c_int, [ctypes.POINTER(JkDesc), c_vp]),
+    "kpgnn_jk_lstm_saved_bytes": (ctypes.c_size_t, [c_i64, c_i32, c_i32, c_i32]),
+    "kpgnn_jk_lstm_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i32, c_i32, c_i32]),
+    "kpgnn_jk_lstm_fwd": (ctypes.c_int, [ctypes.POINTER(JkLstmDesc), c_vp]),
+    "kpgnn_jk_lstm_bwd": (ctypes.c_int, [ctypes.POINTER(JkLstmDesc), c_vp]),
     "kpgnn_attn_pool_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "kpgnn_attn_pool_fwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),
     "kpgnn_attn_pool_bwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),

@@ -15,7 +15,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .layers.gine import GINEConv
-from .ops import (DictPeripheral, attention_pool, dropout_add, embedding_rows, enc_tables, jk_native_applies, jk_reduce,
+from .ops import (DictPeripheral, attention_pool, dropout_add, embedding_rows, enc_tables, jk_lstm_applies, jk_lstm_score,
+                  jk_native_applies, jk_reduce,
                   native_dropout_applies, refuse_dynamic_rows, segment_pool, table_gather_sum, virtual_node_add)
 from .ops_dense import (JKConcatLinear, batch_norm_act, head_linear, jk_concat_linear_nograd, mlp_linear_bn_relu_x2,
                         prepare_mlp_splits, score_head)
@@ -416,8 +417,12 @@ class _KHopBody(nn.Module):
             rep = jk_reduce(h_list, "max") if jk_native_applies(h_list, "max") else torch.stack(h_list, dim=-1).max(dim=-1).values
         elif self.JK == "sum":
             rep = jk_reduce(h_list, "sum") if jk_native_applies(h_list, "sum") else torch.stack(h_list, dim=0).sum(dim=0)
+        elif self.JK == "attention" and jk_lstm_applies(h_list, self.attention_lstm) and jk_native_applies(h_list, "softmax"):
+            # scorer and weighted sum both read the states in place: no stack, no module call (ops.jk_lstm_score, ops.jk_reduce)
+            score = jk_lstm_score(h_list, self.attention_lstm)
+            rep = jk_reduce(h_list, "softmax", score)
         elif self.JK == "attention":
-            # the scoring LSTM keeps its framework module and its stacked input; the weighted sum reads the states in place
+            # the scoring LSTM as a framework module on the stacked states (CPU tensors, hidden size > 16, the switch off)
             hs = torch.stack(h_list, dim=1)
             self.attention_lstm.flatten_parameters()
             score, _ = self.attention_lstm(hs)

@@ -1691,6 +1691,139 @@ def jk_reduce(states, mode, score=None):
     return JKSoftmax.apply(score, *states)
 
 
+# ------------------------------------------------------------------------------------------------ the JK scoring LSTM
+# score [N,S] of the attention readout: nn.LSTM(H, P, bidirectional) over the S states, summed over its 2P outputs (kpgnn.h,
+# kpgnn_jk_lstm_desc).  The states are read in place - no torch.stack, no [N,S,H] gradient of a stack - and what the backward
+# needs is one `saved` buffer in the kernels' own layout.
+_NATIVE_JK_LSTM = True
+_LSTM_PARAMS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0",
+                "weight_ih_l0_reverse", "weight_hh_l0_reverse", "bias_ih_l0_reverse", "bias_hh_l0_reverse")
+
+
+def set_native_jk_lstm(on):
+    """Route the scoring LSTM of JK attention through kpgnn_jk_lstm_* (True, the default) or keep nn.LSTM on the stacked
+    states (False).  Returns the previous setting."""
+    global _NATIVE_JK_LSTM
+    prev, _NATIVE_JK_LSTM = _NATIVE_JK_LSTM, bool(on)
+    return prev
+
+
+def native_jk_lstm():
+    return _NATIVE_JK_LSTM
+
+
+def jk_lstm_applies(states, lstm):
+    """The states as jk_native_applies wants them (CUDA fp32 [N,H], one non-empty shape, 1 <= S <= 32) with H <= 256, and a
+    one-layer, bidirectional, bias-carrying fp32 nn.LSTM(H, P <= 16) without projection on the same device; the switch on."""
+    states = list(states)
+    S = len(states)
+    if not (_NATIVE_JK_LSTM and 1 <= S <= _lib.JK_MAX_STATES and isinstance(lstm, torch.nn.LSTM)):
+        return False
+    shape = states[0].shape
+    if not (all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape == shape for t in states)
+            and states[0].numel() > 0 and shape[1] <= _lib.JK_LSTM_MAX_H):
+        return False
+    return _jk_lstm_module_ok(lstm, shape[1], states[0].device)
+
+
+def _jk_lstm_module_ok(lstm, H, device):
+    """The module half of jk_lstm_applies: one layer, bidirectional, biases, no projection, input_size H, hidden size
+    1 .. 16, fp32 parameters on `device`."""
+    if not (lstm.num_layers == 1 and lstm.bidirectional and lstm.bias and getattr(lstm, "proj_size", 0) == 0
+            and lstm.input_size == H and 1 <= lstm.hidden_size <= _lib.JK_LSTM_MAX_P):
+        return False
+    return all(q.dtype == torch.float32 and q.device == device for q in (getattr(lstm, k) for k in _LSTM_PARAMS))
+
+
+def _jk_lstm_desc(states, params):
+    N, H = states[0].shape
+    d = _lib.JkLstmDesc()
+    d.N, d.H, d.P, d.S = N, H, params[1].shape[1], len(states)
+    for l, t in enumerate(states):
+        d.x[l] = t.data_ptr()
+    d.x_stride = H
+    for k in range(2):
+        d.w_ih[k], d.w_hh[k] = params[4 * k].data_ptr(), params[4 * k + 1].data_ptr()
+        d.b_ih[k], d.b_hh[k] = params[4 * k + 2].data_ptr(), params[4 * k + 3].data_ptr()
+    d.n_dyn = dyn_ptr(N)
+    return d
+
+
+def _jk_lstm_workspace(d, dev):
+    nbytes = _lib.load().kpgnn_jk_lstm_workspace_bytes(d.N, d.H, d.P, d.S)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
+    return ws
+
+
+def _jk_lstm_fwd_launch(states, params, save):
+    """(score [N,S], saved or None): one kpgnn_jk_lstm_fwd call over contiguous states; `saved` only with `save`."""
+    dev = states[0].device
+    d = _jk_lstm_desc(states, params)
+    score = torch.empty((d.N, d.S), dtype=torch.float32, device=dev)
+    d.score = score.data_ptr()
+    saved = None
+    if save:
+        saved = torch.empty(_lib.load().kpgnn_jk_lstm_saved_bytes(d.N, d.H, d.P, d.S), dtype=torch.uint8, device=dev)
+        d.saved = saved.data_ptr()
+    ws = _jk_lstm_workspace(d, dev)
+    _lib.launch("kpgnn_jk_lstm_fwd", dev, ctypes.byref(d))
+    del ws
+    return score, saved
+
+
+class JKLstmScore(torch.autograd.Function):
+    """score = nn.LSTM(states).sum(-1) (kpgnn_jk_lstm_fwd); saves `saved` and references to the states and parameters; the
+    backward is one kpgnn_jk_lstm_bwd call for every state's gradient (views of one [S,N,H] buffer) and the eight parameter
+    gradients (the two biases of a direction share one)."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        params, states = args[:8], args[8:]
+        score, saved = _jk_lstm_fwd_launch(states, params, True)
+        ctx.save_for_backward(saved, *args)
+        return score
+
+    @staticmethod
+    def backward(ctx, gscore):
+        saved, *args = ctx.saved_tensors
+        params, states = args[:8], args[8:]
+        dev = gscore.device
+        d = _jk_lstm_desc(states, params)
+        gscore = gscore.contiguous()
+        d.saved, d.gscore = saved.data_ptr(), gscore.data_ptr()
+        gx = None
+        if any(ctx.needs_input_grad[8:]):
+            gx = torch.empty((d.S, d.N, d.H), dtype=torch.float32, device=dev)
+            d.gx = gx.data_ptr()
+        grads = [torch.empty_like(params[4 * k + j]) for k in range(2) for j in range(3)]     # dw_ih, dw_hh, db per direction
+        for k in range(2):
+            d.dw_ih[k], d.dw_hh[k], d.db[k] = (g.data_ptr() for g in grads[3 * k:3 * k + 3])
+        ws = _jk_lstm_workspace(d, dev)
+        _lib.launch("kpgnn_jk_lstm_bwd", dev, ctypes.byref(d))
+        del ws
+        out = []
+        for k in range(2):
+            dw_ih, dw_hh, db = grads[3 * k:3 * k + 3]
+            out += [dw_ih, dw_hh, db, db.clone()]         # (two leaves must not end up sharing one .grad)
+        out = [g if need else None for g, need in zip(out, ctx.needs_input_grad[:8])]
+        return tuple(out) + tuple(gx[l] if need else None for l, need in enumerate(ctx.needs_input_grad[8:]))
+
+
+def jk_lstm_score(states, lstm):
+    """score [N,S] = lstm(torch.stack(states, 1))[0].sum(-1) for the scoring LSTM of JK attention, the states read in place.
+    Call it where jk_lstm_applies(states, lstm); under no_grad, or when nothing requires a gradient, the entry is launched
+    directly with saved = NULL and no autograd node is made."""
+    if not jk_lstm_applies(states, lstm):
+        raise _lib.KpgnnError("jk_lstm_score: the native route does not apply (jk_lstm_applies); keep nn.LSTM on the stack")
+    states = [t if t.is_contiguous() else t.contiguous() for t in states]
+    params = [getattr(lstm, k) for k in _LSTM_PARAMS]
+    params = [q if q.is_contiguous() else q.contiguous() for q in params]
+    if not torch.is_grad_enabled() or not any(t.requires_grad for t in states + params):
+        return _jk_lstm_fwd_launch([t.detach() for t in states], [q.detach() for q in params], False)[0]
+    return JKLstmScore.apply(*params, *states)
+
+
 class AttentionPool(torch.autograd.Function):
     """PyG's AttentionalAggregation(gate_nn=nn.Linear(D, 1)) over the node ranges of a collated batch (kpgnn_attn_pool_*):
     one launch forward, one plus a fixed-order reduce backward, no atomics."""

@@ -6,8 +6,8 @@ the S = 9 states read in place) and with ops.set_native_jk(False) (the torch.sta
     python scripts/jk_step.py --variant native        # one run of one variant in this process (what the pairs start)
     python scripts/jk_step.py --variant native --jk max --no-graph --steps 5      # e.g. under a kernel trace
 
-sum and max are timed eagerly and as one captured hipGraph; attention eagerly only (its scoring LSTM stays a framework module
-and capturing that is not this script's business).  Per run: `--steps` steps after `--warmup`, each bracketed by two HIP
+sum and max are timed eagerly and as one captured hipGraph; attention eagerly only here (scripts/jk_lstm_step.py times its
+scoring LSTM, native against the framework module, and captures the native step).  Per run: `--steps` steps after `--warmup`, each bracketed by two HIP
 events; the run's figure is the median step.  Also per run: torch.cuda.max_memory_allocated over the eager steps, the C-ABI
 launches of one eager step (name: count, in order of first appearance), and the bytes the reduce needs per direction, counted
 from the shapes.  Reported per variant: the median over the runs and their spread (min .. max)."""
