@@ -1225,6 +1225,50 @@ size_t kpgnn_jk_lstm_workspace_bytes(int64_t N, int32_t H, int32_t P, int32_t S)
 int kpgnn_jk_lstm_fwd(const kpgnn_jk_lstm_desc* d, kpgnn_stream_t stream);
 int kpgnn_jk_lstm_bwd(const kpgnn_jk_lstm_desc* d, kpgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The bodies' norms other than BatchNorm (csrc/body_norm.hip; models/GNNs.py:103-112, norm_type "Layer", "Instance",
+ * "GraphSize", "Pair").  The bodies call every norm WITHOUT a batch vector, so PyG's modules take the whole batch as one
+ * graph; with x [N,C], n the live row count and eps added as PyG adds it:
+ *   KPGNN_NORM_LAYER      mu, sd = mean and biased standard deviation over all n*C elements;
+ *                         out = (x - mu) / (sd + eps) * weight[c] + bias[c]                  (eps joins the std, not the variance)
+ *   KPGNN_NORM_INSTANCE   per column: out = (x - mean_n) / sqrt(var_biased_n + eps)          (no affine, no running statistics)
+ *   KPGNN_NORM_GRAPHSIZE  out = x / sqrt(n)
+ *   KPGNN_NORM_PAIR       xc = x - mean_n per column; out = xc / sqrt(eps + mean_n(sum_c xc^2))
+ * each (+ residual[n,c] when given).  None has running statistics: training and evaluation compute the same.
+ *   fwd: column sums of x and x^2 in DOUBLE as per-block partials in `workspace`, added in block order by a one-block finalize
+ *        that leaves the fp32 coefficients in `saved`, then one streaming pass out = (x - m[c]) * s[c] (centred: a constant
+ *        column and n == 1 give exact zeros).  saved: [0,C) m[c], [C,2C) s[c], then {mu, s, sd, n} (LAYER) / {0, r, 0, n}.
+ *        Three launches; GRAPHSIZE one.
+ *   bwd: the same three steps over the column sums of gout and gout*x: writes gx, and for LAYER gweight / gbias where given.
+ *        The residual's gradient is gout itself - the caller returns it, nothing is launched for it.
+ * No atomics: the same inputs and capacity give the same bits.  Rows at or beyond *n_dyn are not read, written or summed, in
+ * any output of either direction; n is *n_dyn where given.  1 <= C <= 256 (KPGNN_EINVAL below, KPGNN_ELIMIT above); N == 0
+ * launches nothing.  `workspace` (kpgnn_body_norm_workspace_bytes, 16-byte aligned) need not be zeroed.
+ * Both entries validate one way for every kind: x, saved and workspace must be non-NULL (x_stride >= C) also where a kind
+ * does not read them - the GRAPHSIZE backward reads gout alone and writes gx alone; any valid pointer serves as its x.
+ * ---------------------------------------------------------------------------------------------- */
+enum { KPGNN_NORM_LAYER = 0, KPGNN_NORM_INSTANCE = 1, KPGNN_NORM_GRAPHSIZE = 2, KPGNN_NORM_PAIR = 3 };
+
+typedef struct kpgnn_norm_desc {
+    int64_t N; int32_t C, kind; float eps;         /* rows (capacity with n_dyn), row width (1 .. 256), KPGNN_NORM_*, 1e-5 */
+    const float* x; int64_t x_stride;              /* device [N,C], row stride in floats (>= C); both directions */
+    const float* weight; const float* bias;        /* device [C]: LAYER (weight required, bias optional); NULL elsewhere */
+    const float* residual; int64_t res_stride;     /* optional device [N,C] added to out (fwd) */
+    float* out; int64_t out_stride;                /* device [N,C] (fwd) */
+    float* saved;                                  /* device float [2C + 4]: fwd out, bwd in */
+    /* backward only */
+    const float* gout; int64_t gout_stride;        /* device [N,C] */
+    float* gx; int64_t gx_stride;                  /* device [N,C] */
+    float* gweight; float* gbias;                  /* device [C], optional (LAYER) */
+    void* workspace; size_t workspace_bytes;       /* >= kpgnn_body_norm_workspace_bytes(N, C) */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= N; kpgnn_wgrad_desc explains); NULL: all N rows */
+} kpgnn_norm_desc;
+
+/* 0 = the shape is not covered. */
+size_t kpgnn_body_norm_workspace_bytes(int64_t N, int32_t C);
+int kpgnn_body_norm_fwd(const kpgnn_norm_desc* d, kpgnn_stream_t stream);
+int kpgnn_body_norm_bwd(const kpgnn_norm_desc* d, kpgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -346,6 +346,20 @@ class JkLstmDesc(ctypes.Structure):
 
 JK_LSTM_MAX_P, JK_LSTM_MAX_H = 16, 256    # csrc/jk_lstm.hip kMaxP, kMaxH (S: JK_MAX_STATES)
 
+NORM_LAYER, NORM_INSTANCE, NORM_GRAPHSIZE, NORM_PAIR = 0, 1, 2, 3     # include/kpgnn.h KPGNN_NORM_*
+NORM_MAX_C = 256                                                      # csrc/body_norm.hip kMaxC
+
+
+class NormDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("C", c_i32), ("kind", c_i32), ("eps", ctypes.c_float),
+        ("x", c_vp), ("x_stride", c_i64), ("weight", c_vp), ("bias", c_vp), ("residual", c_vp), ("res_stride", c_i64),
+        ("out", c_vp), ("out_stride", c_i64), ("saved", c_vp),
+        ("gout", c_vp), ("gout_stride", c_i64), ("gx", c_vp), ("gx_stride", c_i64), ("gweight", c_vp), ("gbias", c_vp),
+        ("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t),
+        ("n_dyn", c_vp),
+    ]
+
 
 class AttnPoolDesc(ctypes.Structure):
     _fields_ = [
@@ -461,6 +475,9 @@ SIGNATURES = {
     "kpgnn_jk_lstm_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i32, c_i32, c_i32]),
     "kpgnn_jk_lstm_fwd": (ctypes.c_int, [ctypes.POINTER(JkLstmDesc), c_vp]),
     "kpgnn_jk_lstm_bwd": (ctypes.c_int, [ctypes.POINTER(JkLstmDesc), c_vp]),
+    "kpgnn_body_norm_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i32]),
+    "kpgnn_body_norm_fwd": (ctypes.c_int, [ctypes.POINTER(NormDesc), c_vp]),
+    "kpgnn_body_norm_bwd": (ctypes.c_int, [ctypes.POINTER(NormDesc), c_vp]),
     "kpgnn_attn_pool_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "kpgnn_attn_pool_fwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),
     "kpgnn_attn_pool_bwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),

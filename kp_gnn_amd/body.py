@@ -6,7 +6,9 @@ the *callers* of the path this package accelerates; with PyG installed they run 
 kp_gnn_amd.layers.  PyG is absent here and on the GPU box, so bench.py / smoke() / the body-level parity
 tests need a caller of their own: this file.  It keeps the reference's constructor arguments and
 state_dict key names (so reference checkpoints and the golden bodies load verbatim) but shares one base
-class instead of three near-identical copies, and only implements norm_type="Batch".
+class instead of three near-identical copies.  All five norm_type choices of the reference are built: "Batch" on the
+BatchNorm kernels, "Layer", "Instance", "GraphSize" and "Pair" on ops.body_norm (PyG's modules as the bodies call them: without
+a batch vector, the whole batch one graph).
 """
 import copy
 
@@ -15,7 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .layers.gine import GINEConv
-from .ops import (DictPeripheral, attention_pool, dropout_add, embedding_rows, enc_tables, jk_lstm_applies, jk_lstm_score,
+from .ops import (DictPeripheral, attention_pool, body_norm, dropout_add, embedding_rows, enc_tables, jk_lstm_applies, jk_lstm_score,
                   jk_native_applies, jk_reduce,
                   native_dropout_applies, refuse_dynamic_rows, segment_pool, table_gather_sum, virtual_node_add)
 from .ops_dense import (JKConcatLinear, batch_norm_act, head_linear, jk_concat_linear_nograd, mlp_linear_bn_relu_x2,
@@ -237,6 +239,79 @@ class BatchNorm(nn.Module):
         return batch_norm_act(x, self.module, relu=False, residual=residual)
 
 
+class LayerNorm(nn.Module):
+    """PyG's LayerNorm(in_channels) (mode "graph", affine) called without a batch vector: mean and biased standard deviation
+    over all N * C elements, eps added to the standard deviation.  state_dict keys weight / bias, as PyG's module yields."""
+
+    def __init__(self, in_channels, eps=1e-5):
+        super().__init__()
+        self.in_channels, self.eps = in_channels, eps
+        self.weight = nn.Parameter(torch.empty(in_channels))
+        self.bias = nn.Parameter(torch.empty(in_channels))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.ones_(self.weight)
+        nn.init.zeros_(self.bias)
+
+    def forward(self, x, residual=None):
+        return body_norm(x, "Layer", self.weight, self.bias, residual=residual, eps=self.eps)
+
+
+class InstanceNorm(nn.Module):
+    """PyG's InstanceNorm(in_channels) (affine=False, track_running_stats=False) called without a batch vector: every column
+    normalised over the N rows, the same in training and evaluation.  No parameters, no buffers."""
+
+    def __init__(self, in_channels, eps=1e-5):
+        super().__init__()
+        self.in_channels, self.eps = in_channels, eps
+
+    def reset_parameters(self):
+        pass
+
+    def forward(self, x, residual=None):
+        return body_norm(x, "Instance", residual=residual, eps=self.eps)
+
+
+class GraphSizeNorm(nn.Module):
+    """PyG's GraphSizeNorm() called without a batch vector: x / sqrt(N)."""
+
+    def reset_parameters(self):
+        pass
+
+    def forward(self, x, residual=None):
+        return body_norm(x, "GraphSize", residual=residual)
+
+
+class PairNorm(nn.Module):
+    """PyG's PairNorm() (scale=1, scale_individually=False) called without a batch vector."""
+
+    def __init__(self, eps=1e-5):
+        super().__init__()
+        self.eps = eps
+
+    def reset_parameters(self):
+        pass
+
+    def forward(self, x, residual=None):
+        return body_norm(x, "Pair", residual=residual, eps=self.eps)
+
+
+def _make_norm(norm_type, hidden_size):
+    """One norm of models/GNNs.py:103-112."""
+    if norm_type == "Batch":
+        return BatchNorm(hidden_size)
+    if norm_type == "Layer":
+        return LayerNorm(hidden_size)
+    if norm_type == "Instance":
+        return InstanceNorm(hidden_size)
+    if norm_type == "GraphSize":
+        return GraphSizeNorm()
+    if norm_type == "Pair":
+        return PairNorm()
+    raise ValueError("Not supported norm method")
+
+
 def _vn_mlp(h):
     return nn.Sequential(nn.Linear(h, h), nn.BatchNorm1d(h), nn.ReLU(), nn.Linear(h, h), nn.BatchNorm1d(h), nn.ReLU())
 
@@ -280,11 +355,7 @@ class _KHopBody(nn.Module):
             self.peripheral_configuration_embedding = FeatureConcatEncoder(
                 [max_distance_count + 1] * (max_hop_num + 1), width, padding=False)
             self.pcw = nn.Parameter(torch.rand(1))
-        if norm_type != "Batch":
-            if norm_type in ("Layer", "Instance", "GraphSize", "Pair"):
-                raise NotImplementedError(f"norm_type={norm_type} is a PyG module; only 'Batch' is provided here")
-            raise ValueError("Not supported norm method")
-        self.norms = nn.ModuleList(BatchNorm(hidden_size) for _ in range(num_layer))
+        self.norms = nn.ModuleList(_make_norm(norm_type, hidden_size) for _ in range(num_layer))
 
     # -- parameter init shared by the three bodies (GNNs.py:122-140)
     def _reset_common(self):

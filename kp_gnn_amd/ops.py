@@ -1824,6 +1824,162 @@ def jk_lstm_score(states, lstm):
     return JKLstmScore.apply(*params, *states)
 
 
+# ------------------------------------------------------------------------------------------------ the bodies' other norms
+# norm_type "Layer", "Instance", "GraphSize", "Pair" (models/GNNs.py:103-112; kpgnn.h, kpgnn_norm_desc): PyG's modules called
+# without a batch vector, so the whole batch is one graph.  None has running statistics (training and evaluation compute the
+# same), and what the backward keeps besides x is a float [2C + 4] of coefficients.
+NORM_KINDS = {"Layer": _lib.NORM_LAYER, "Instance": _lib.NORM_INSTANCE, "GraphSize": _lib.NORM_GRAPHSIZE, "Pair": _lib.NORM_PAIR}
+_NATIVE_NORMS = True
+# per kind, on EXACT-SHAPE batches: GraphSize is one framework launch per direction to begin with, and an eager step measured
+# 0.08 - 0.12 ms slower with the native one (a captured step the same to 0.04 ms faster) - opt-in, as dropout is.  Inside a dynamic_rows
+# block every kind is native whatever this says: it is the only route there.
+_NATIVE_NORM_EXACT = {"Layer": True, "Instance": True, "GraphSize": False, "Pair": True}
+
+
+def set_native_norms(on):
+    """Route the Layer / Instance / GraphSize / Pair norms of fp32 device rows through kpgnn_body_norm_* (True, the default) or
+    keep the framework expressions for all of them (False).  Returns the previous setting."""
+    global _NATIVE_NORMS
+    prev, _NATIVE_NORMS = _NATIVE_NORMS, bool(on)
+    return prev
+
+
+def native_norms():
+    return _NATIVE_NORMS
+
+
+def set_native_norm_exact(kind, on):
+    """Whether `kind` takes the native route on EXACT-SHAPE batches too, given that the switch (set_native_norms) is on; default:
+    every kind but "GraphSize".  Inside a dynamic_rows block every kind is native whatever this says.  Returns the previous
+    setting of that kind."""
+    if kind not in NORM_KINDS:
+        raise ValueError(f"norm kind must be one of {sorted(NORM_KINDS)}, got {kind!r}")
+    prev, _NATIVE_NORM_EXACT[kind] = _NATIVE_NORM_EXACT[kind], bool(on)
+    return prev
+
+
+def native_norm_exact(kind):
+    """Whether `kind` is native on an exact-shape batch as things are set (the switch and the kind's own setting)."""
+    return bool(_NATIVE_NORMS and _NATIVE_NORM_EXACT[kind])
+
+
+def body_norm_applies(x):
+    """fp32 device rows [N,C] with N >= 1 and 1 <= C <= 256 (what csrc/body_norm.hip covers)."""
+    return bool(x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and 1 <= x.shape[1] <= _lib.NORM_MAX_C)
+
+
+def body_norm_reference(x, kind, weight=None, bias=None, residual=None, eps=1e-5):
+    """The framework expression of the four norms (any device, any floating dtype): what PyG's LayerNorm (mode "graph"),
+    InstanceNorm (no affine, no running statistics), GraphSizeNorm and PairNorm (scale 1) compute without a batch vector."""
+    if kind == "Layer":
+        xc = x - x.mean()
+        y = xc / (xc.std(unbiased=False) + eps) * weight + bias
+    elif kind == "Instance":
+        y = (x - x.mean(0, keepdim=True)) / (x.var(0, unbiased=False, keepdim=True) + eps).sqrt()
+    elif kind == "GraphSize":
+        y = x / x.shape[0] ** 0.5
+    elif kind == "Pair":
+        xc = x - x.mean(0, keepdim=True)
+        y = xc / (eps + xc.pow(2).sum(-1).mean()).sqrt()
+    else:
+        raise ValueError(f"norm kind must be one of {sorted(NORM_KINDS)}, got {kind!r}")
+    return y if residual is None else y + residual
+
+
+def _norm_desc(x, kind, eps, saved):
+    """(descriptor, workspace): x rows the kernels can walk, the coefficient buffer and a workspace of the entry's size."""
+    N, C = x.shape
+    d = _lib.NormDesc()
+    d.N, d.C, d.kind, d.eps = N, C, NORM_KINDS[kind], eps
+    d.x, d.x_stride, d.saved = x.data_ptr(), x.stride(0), saved.data_ptr()
+    nbytes = _lib.load().kpgnn_body_norm_workspace_bytes(N, C)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
+    d.n_dyn = dyn_ptr(N)
+    return d, ws
+
+
+def _norm_fwd_launch(x, kind, weight, bias, residual, eps):
+    """(out, saved, x as the kernels read it): one kpgnn_body_norm_fwd call."""
+    N, C = x.shape
+    x = _rows_view(x, C)
+    out = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    saved = torch.empty(2 * C + 4, dtype=torch.float32, device=x.device)
+    d, ws = _norm_desc(x, kind, eps, saved)
+    d.out, d.out_stride = out.data_ptr(), C
+    if kind == "Layer":
+        weight, bias = weight.contiguous(), bias.contiguous()
+        d.weight, d.bias = weight.data_ptr(), bias.data_ptr()
+    if residual is not None:
+        residual = _rows_view(residual, C)
+        d.residual, d.res_stride = residual.data_ptr(), residual.stride(0)
+    _lib.launch("kpgnn_body_norm_fwd", x.device, ctypes.byref(d))
+    del ws
+    return out, saved, x
+
+
+class BodyNorm(torch.autograd.Function):
+    """out = norm(x) (+ residual): one kpgnn_body_norm_fwd call forward, one kpgnn_body_norm_bwd call backward.  Saves x (which
+    autograd holds anyway; not for GraphSize), Layer's weight and the float [2C + 4] coefficients; the residual's gradient is
+    the incoming one."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, kind, eps):
+        out, saved, x = _norm_fwd_launch(x, kind, weight, bias, residual, eps)
+        # (GraphSize's backward is gout / sqrt(n): it does not read x, so x is not kept alive for it)
+        ctx.save_for_backward(*(() if kind == "GraphSize" else (x,)), saved, *(() if weight is None else (weight,)))
+        ctx.kind, ctx.eps = kind, eps
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        N, C = gout.shape
+        gout_rows = _rows_view(gout, C)
+        if ctx.kind == "GraphSize":
+            (saved,), x, w = ctx.saved_tensors, gout_rows, []       # (the descriptor wants some x; this kind never reads it)
+        else:
+            x, saved, *w = ctx.saved_tensors
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        gx = gw = gb = None
+        if need_x or need_w or need_b:
+            d, ws = _norm_desc(x, ctx.kind, ctx.eps, saved)
+            gx = torch.empty((N, C), dtype=torch.float32, device=x.device)
+            d.gout, d.gout_stride, d.gx, d.gx_stride = gout_rows.data_ptr(), gout_rows.stride(0), gx.data_ptr(), C
+            if w:
+                weight = w[0].contiguous()
+                gw, gb = torch.empty_like(weight), torch.empty_like(weight)
+                d.weight, d.gweight, d.gbias = weight.data_ptr(), gw.data_ptr(), gb.data_ptr()
+            _lib.launch("kpgnn_body_norm_bwd", x.device, ctypes.byref(d))
+            del ws
+        return (gx if need_x else None, gw if need_w else None, gb if need_b else None, gout if need_r else None, None, None)
+
+
+def body_norm(x, kind, weight=None, bias=None, residual=None, eps=1e-5):
+    """The Layer / Instance / GraphSize / Pair norm of the bodies over the rows x [N,C] (+ residual), the whole batch as one
+    graph; weight / bias [C] go with "Layer" and with no other kind.  Where body_norm_applies and the switch is on
+    (set_native_norms; "GraphSize" on exact-shape batches only after set_native_norm_exact("GraphSize", True), inside a dynamic_rows
+    block always), one kpgnn_body_norm_fwd call and one kpgnn_body_norm_bwd call - the statistics are over the LIVE rows of
+    a dynamic_rows block, and rows beyond them are left alone; under no_grad, or when nothing requires a gradient, no autograd
+    node is made.  Everything else - CPU tensors, other dtypes, C > 256, the switch off - keeps the framework expression
+    (body_norm_reference), which has no dynamic row count."""
+    if kind not in NORM_KINDS:
+        raise ValueError(f"norm kind must be one of {sorted(NORM_KINDS)}, got {kind!r}")
+    if (kind == "Layer") != (weight is not None and bias is not None) or (kind != "Layer" and (weight is not None or bias is not None)):
+        raise ValueError("body_norm: weight and bias go with kind 'Layer' and with no other")
+    native = _NATIVE_NORMS and body_norm_applies(x) and (_NATIVE_NORM_EXACT[kind] or dyn_ptr(x.shape[0]) is not None)
+    for t in (weight, bias):
+        native = native and (t is None or (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (x.shape[1],)))
+    native = native and (residual is None or (residual.is_cuda and residual.dtype == torch.float32 and residual.shape == x.shape))
+    if not native:
+        if x.dim() == 2:
+            refuse_dynamic_rows(f"the framework expression of the {kind} norm", x.shape[0])
+        return body_norm_reference(x, kind, weight, bias, residual, eps)
+    eps = float(eps)
+    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (x, weight, bias, residual)):
+        return _norm_fwd_launch(x.detach(), kind, weight, bias, residual, eps)[0]      # no autograd node, nothing saved
+    return BodyNorm.apply(x, weight, bias, residual, kind, eps)
+
+
 class AttentionPool(torch.autograd.Function):
     """PyG's AttentionalAggregation(gate_nn=nn.Linear(D, 1)) over the node ranges of a collated batch (kpgnn_attn_pool_*):
     one launch forward, one plus a fixed-order reduce backward, no atomics."""
