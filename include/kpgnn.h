@@ -1097,6 +1097,55 @@ int kpgnn_hop_mlp_fwd(const kpgnn_hop_mlp_desc* d, kpgnn_stream_t stream);
 int kpgnn_hop_mlp_bwd(const kpgnn_hop_mlp_desc* d, kpgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * KP-GraphSAGE tail: per-hop projection of [x | x_n], ReLU, L2-normalise (+ geometric hop-combine (+ combine_proj))
+ * (reference layers/KPGraphSAGE.py:88-96, combine.py:52-58).  With W [K, 2*DI, DO]:
+ *     z[n,k,:]  = x[n,k,:] W[k][:DI] + xn[n,k,:] W[k][DI:] + b[k]      (the concatenation is never materialised)
+ *     r = max(z, 0);  nrm[n,k] = sqrt(sum_j r[n,k,j]^2);  rinv[n,k] = 1 / max(nrm, 1e-12)
+ *     y[n,k,:]  = r[n,k,:] / max(nrm[n,k], 1e-12)                      (F.normalize(relu(z), p=2, dim=-1); by division:
+ *                                                                       a row with one positive entry is exactly 1)
+ *     comb[n,:] = sum_k theta[k,:] * y[n,k,:]        (only with theta; otherwise y [N,K,DO] is the result)
+ *     out[n,:]  = comb[n,:] Wc^T + bc                (only with wc: H outputs; otherwise comb [N,DO] is the result)
+ * The same plan as kpgnn_hop_mlp_*: a block keeps a 32-node tile of x and of xn in LDS next to the zero-padded weights,
+ * every product is v_mfma_f32_16x16x4_f32 (exact fp32), the row norm is summed in the accumulator registers, and x, xn, y,
+ * out cross HBM once per direction.
+ *   fwd: writes y and rinv (saved for backward) and out ([N,H] with wc, [N,DO] with theta only).  With theta, y and rinv
+ *        may both be NULL (evaluation: nothing is written but out; out has the same bits either way).
+ *   bwd: gout is [N,H] with wc, [N,DO] with theta only, [N,K,DO] otherwise.  With gy = d(y):
+ *            gr = rinv * (gy - y <gy, y>)  where nrm > 1e-12,   gr = gy * 1e12  where the clamp was active
+ *            gz = gr * [y > 0]             (a slot whose ReLU output is all zero: y = 0 and gz = 0, no NaN / Inf)
+ *        writes gx = gz W[k][:DI]^T and gxn = gz W[k][DI:]^T (two [N,K,DI] tensors) and
+ *        gflat = [ dW (K*2DI*DO) | db (K*DO) | dtheta (K*DO, with theta) | dWc (H*DO) | dbc (H) (with wc) ],
+ *        per-block partials added in block order (deterministic, no atomics).
+ * Every row's y / out / gx / gxn depends on that row alone (not on N or the grid).
+ * Limits (KPGNN_ELIMIT beyond): DI, DO <= 32; K * ceil(max(DI,DO)/16)^2 <= 32; H <= 1024 and
+ * ceil(H/16) * ceil(max(DI,DO)/16) <= 32; K*max(DI,DO) <= 1024; the LDS footprint (<= 160 KB).
+ * N == 0: fwd launches nothing, bwd zero-fills gflat.  No dynamic row count (n_dyn).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct kpgnn_sage_tail_desc {
+    int64_t N;
+    int32_t K, DI, DO;
+    int32_t H;                              /* combine_proj outputs; 0 = no projection (H > 0 exactly when wc is given) */
+    const float* x; const float* xn;        /* device [N,K,DI] contiguous: the (path-encoded) input and its aggregation */
+    const float* w; const float* b;         /* device [K,2*DI,DO], [K,DO] */
+    const float* theta;                     /* device [K,DO] or NULL */
+    const float* wc; const float* bc;       /* device [H,DO], [H] (bc may be NULL); wc needs theta */
+    float* y;                               /* device [N,K,DO] contiguous (fwd: out, bwd: in) */
+    float* rinv;                            /* device [N,K] (fwd: out, bwd: in) */
+    float* out;                             /* device [N,H] / [N,DO] (fwd, with theta) */
+    /* backward only */
+    const float* gout;                      /* device [N,H] / [N,DO] / [N,K,DO] */
+    float* gx; float* gxn;                  /* device [N,K,DI] each */
+    float* gflat;                           /* device, layout above */
+    void* workspace; size_t workspace_bytes;  /* >= kpgnn_sage_tail_workspace_bytes(N, K, DI, DO, H) */
+} kpgnn_sage_tail_desc;
+
+/* Backward grid x slab width x 4 bytes, the slab width counted with the dtheta block:
+ * K*2*DI*DO + 2*K*DO + H*DO + H floats.  0 = the shape is not covered (the caller keeps the framework tail). */
+size_t kpgnn_sage_tail_workspace_bytes(int64_t N, int32_t K, int32_t DI, int32_t DO, int32_t H);
+int kpgnn_sage_tail_fwd(const kpgnn_sage_tail_desc* d, kpgnn_stream_t stream);
+int kpgnn_sage_tail_bwd(const kpgnn_sage_tail_desc* d, kpgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Dropout (+ residual) with counter-based masks (csrc/dropout.hip; models/GNNs.py, the self.dropout sites):
  *   fwd:  out[n,c] = keep ? fmaf(x[n,c], scale, residual[n,c]) : residual[n,c]      (no residual: x * scale / 0)
  *   bwd:  out[n,c] = keep ? x[n,c] * scale : 0         with x := dL/dout, out := dL/dx; the residual branch's gradient is

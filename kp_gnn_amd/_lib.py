@@ -265,6 +265,15 @@ class HopMlpDesc(ctypes.Structure):
     ]
 
 
+class SageTailDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("K", c_i32), ("DI", c_i32), ("DO", c_i32), ("H", c_i32),
+        ("x", c_vp), ("xn", c_vp), ("w", c_vp), ("b", c_vp), ("theta", c_vp), ("wc", c_vp), ("bc", c_vp),
+        ("y", c_vp), ("rinv", c_vp), ("out", c_vp), ("gout", c_vp), ("gx", c_vp), ("gxn", c_vp), ("gflat", c_vp),
+        ("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 class TgsDesc(ctypes.Structure):
     _fields_ = [
         ("M", c_i64), ("C", c_i32), ("D", c_i32), ("R", c_i32),
@@ -501,6 +510,9 @@ SIGNATURES = {
     "kpgnn_hop_mlp_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i32, c_i32, c_i32, c_i32]),
     "kpgnn_hop_mlp_fwd": (ctypes.c_int, [ctypes.POINTER(HopMlpDesc), c_vp]),
     "kpgnn_hop_mlp_bwd": (ctypes.c_int, [ctypes.POINTER(HopMlpDesc), c_vp]),
+    "kpgnn_sage_tail_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i32, c_i32, c_i32, c_i32]),
+    "kpgnn_sage_tail_fwd": (ctypes.c_int, [ctypes.POINTER(SageTailDesc), c_vp]),
+    "kpgnn_sage_tail_bwd": (ctypes.c_int, [ctypes.POINTER(SageTailDesc), c_vp]),
     "kpgnn_table_gather_sum_fwd": (ctypes.c_int, [ctypes.POINTER(TgsDesc), c_vp]),
     "kpgnn_table_gather_sum_bwd": (ctypes.c_int, [ctypes.POINTER(TgsDesc), c_vp]),
     "kpgnn_table_gather_sum_bwd_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i32, c_i32]),

@@ -805,6 +805,96 @@ def hop_mlp(s, w1, b1, w2, b2, theta=None, wc=None, bc=None):
     return HopMlp.apply(s, w1, b1, w2, b2, theta, wc, bc)
 
 
+# ------------------------------------------- KP-GraphSAGE projection + ReLU + L2-normalise (+ geometric combine + projection)
+_NATIVE_SAGE_TAIL = True
+
+
+def set_native_sage_tail(on):
+    """Route KPGraphSAGEConv's dense tail to kpgnn_sage_tail_* (True) or keep the framework expression (False).  Returns the
+    previous setting.  Layers decide their route on the first forward after a change."""
+    global _NATIVE_SAGE_TAIL
+    prev, _NATIVE_SAGE_TAIL = _NATIVE_SAGE_TAIL, bool(on)
+    return prev
+
+
+def native_sage_tail():
+    return _NATIVE_SAGE_TAIL
+
+
+class SageTail(torch.autograd.Function):
+    """normalize(relu(x W[:DI] + xn W[DI:] + b)) per hop (+ sum_k theta_k * . (+ combine_proj)), one HIP launch per direction
+    (sage_tail.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, xn, w, b, theta, wc, bc):
+        x, xn = x.contiguous(), xn.contiguous()
+        N, K, DI = x.shape
+        refuse_dynamic_rows("kpgnn_sage_tail", N)
+        DO = w.shape[2]
+        H = wc.shape[0] if wc is not None else 0
+        dev = x.device
+        w, b = w.contiguous(), b.contiguous()
+        theta = theta.contiguous() if theta is not None else None
+        wc = wc.contiguous() if wc is not None else None
+        bc = bc.contiguous() if bc is not None else None
+        save = theta is None or any(ctx.needs_input_grad)      # (under no_grad with theta nothing is written but out)
+        y = torch.empty((N, K, DO), dtype=torch.float32, device=dev) if save else None
+        rinv = torch.empty((N, K), dtype=torch.float32, device=dev) if save else None
+        out = torch.empty((N, H if H else DO), dtype=torch.float32, device=dev) if theta is not None else None
+        d = _lib.SageTailDesc()
+        d.N, d.K, d.DI, d.DO, d.H = N, K, DI, DO, H
+        d.x, d.xn, d.w, d.b, d.theta = x.data_ptr(), xn.data_ptr(), w.data_ptr(), b.data_ptr(), _ptr(theta)
+        d.wc, d.bc = _ptr(wc), _ptr(bc)
+        d.y, d.rinv, d.out = _ptr(y), _ptr(rinv), _ptr(out)
+        _lib.launch("kpgnn_sage_tail_fwd", dev, ctypes.byref(d))
+        if save:
+            ctx.save_for_backward(x, xn, w, b, theta, wc, bc, y, rinv)
+        return out if theta is not None else y
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, xn, w, b, theta, wc, bc, y, rinv = ctx.saved_tensors
+        lib = _lib.load()
+        N, K, DI = x.shape
+        DO = w.shape[2]
+        H = wc.shape[0] if wc is not None else 0
+        dev = x.device
+        gout = gout.contiguous()
+        g = torch.empty((2, N, K, DI), dtype=torch.float32, device=dev)
+        sizes = [K * 2 * DI * DO, K * DO] + ([K * DO] if theta is not None else []) + ([H * DO, H] if H else [])
+        gflat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        ws_bytes = int(lib.kpgnn_sage_tail_workspace_bytes(max(N, 1), K, DI, DO, H))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        d = _lib.SageTailDesc()
+        d.N, d.K, d.DI, d.DO, d.H = N, K, DI, DO, H
+        d.x, d.xn, d.w, d.b, d.theta = x.data_ptr(), xn.data_ptr(), w.data_ptr(), b.data_ptr(), _ptr(theta)
+        d.wc, d.bc = _ptr(wc), _ptr(bc)
+        d.y, d.rinv = y.data_ptr(), rinv.data_ptr()
+        d.gout, d.gx, d.gxn, d.gflat = gout.data_ptr(), g[0].data_ptr(), g[1].data_ptr(), gflat.data_ptr()
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws_bytes
+        _lib.launch("kpgnn_sage_tail_bwd", dev, ctypes.byref(d))
+        parts = list(torch.split(gflat, sizes))
+        gth = parts[2].view(K, DO) if theta is not None else None
+        gwc = parts[-2].view(H, DO) if H else None
+        gbc = parts[-1] if (H and bc is not None) else None
+        return g[0], g[1], parts[0].view(K, 2 * DI, DO), parts[1].view(K, DO), gth, gwc, gbc
+
+
+def sage_tail_supported(K, DI, DO, H=0):
+    """Whether kpgnn_sage_tail_* covers the shape (wider hops keep the batched-matmul expression)."""
+    return int(_lib.load().kpgnn_sage_tail_workspace_bytes(1, K, DI, DO, H)) > 0
+
+
+def sage_tail(x, xn, w, b, theta=None, wc=None, bc=None):
+    """x, xn [N,K,DI], w [K,2*DI,DO], b [K,DO] -> y = normalize(relu([x | xn] w + b)) [N,K,DO] (theta None),
+    comb [N,DO] = sum_k theta[k] * y[:,k] (theta), or comb wc^T + bc [N,H] (theta and wc)  (reference KPGraphSAGE.py:88-96)."""
+    if not (x.is_cuda and xn.is_cuda):
+        raise _lib.KpgnnError("sage_tail needs device tensors: there is no CPU path")
+    if wc is not None and theta is None:
+        raise _lib.KpgnnError("sage_tail: the projection needs theta")
+    return SageTail.apply(x, xn, w, b, theta, wc, bc)
+
+
 # ------------------------------------------------------------------------------------ geometric hop-combine weights
 class GeoTheta(torch.autograd.Function):
     """theta[k,d] = softmax_k(a (1-a)^k), a = sigmoid(alphas[d])  (combine.py:43-50): one launch per direction."""
