@@ -43,6 +43,12 @@ template <int VEC> struct V {
     __device__ __forceinline__ void fma(float s, const V& o) { for (int i = 0; i < VEC; ++i) v[i] = fmaf(s, o.v[i], v[i]); }
 };
 
+// base + a 32-bit BYTE offset: the form that becomes a scalar base with a 32-bit lane offset in the instruction, so that no
+// per-thread 64-bit address (base + lane's columns) is kept in registers across the node loop
+template <typename T> __device__ __forceinline__ T* at_byte(T* base, uint32_t off) {
+    return reinterpret_cast<T*>(reinterpret_cast<char*>(const_cast<typename std::remove_const<T>::type*>(base)) + (size_t)off);
+}
+
 __device__ __forceinline__ float gelu_exact(float x) {  // F.gelu(approximate='none'), erf to 5e-7 abs
     float e2;
     return 0.5f * x * (1.0f + fast_erf(x * 0.70710678118654752440f, &e2));
@@ -72,13 +78,17 @@ struct FwdParams {
     const float* ptab; const int32_t* uid; int64_t uid_stride;
     const float* xs[16];        // per-hop inputs (x == NULL)
     int lds_theta, lds_ptab;    // floats of theta / ptab staged in LDS behind the code tables (TAB == 1), 0 = read from global
+    int fast;                   // host only: the FAST instantiation runs (decided where the LDS is sized, kpgnn_aggregate_fwd)
 };
 
 // TAB: 0 = no tables, 1 = tables in LDS, 2 = tables read from global (too large for LDS).
 // GCN selects the weighted inner loop; the other epilogues are wave-uniform runtime switches.
 // FAST: the KP-GIN+ training configuration (GELU epilogue, fused geometric combine, dictionary P, S saved) with its
-// epilogue switches resolved at compile time.
-// BF (FAST only): the gathered hop slots (xs) and the saved S (`pre`) are bf16 rows; sums, tables, theta, P, hout fp32.
+// epilogue switches resolved at compile time.  The host launches it only with theta staged in LDS and K < G (row pointers
+// and dictionary ids of a node sit in its sub-group's lanes); its hop epilogue then waits for LDS reads only: the
+// dictionary row is requested one hop ahead with the neighbour rows, the S row is stored one hop late.
+// BF (the KP-GIN+ training epilogue, FAST or not): the gathered hop slots (xs) and the saved S (`pre`) are bf16 rows; sums,
+// tables, theta, P, hout fp32.
 // PULL: the pull form of the backward gather (kpgnn_khop_pull_gather) resolved at compile time - mode SUM, per-hop slabs,
 // hop sums added with unit weights (no theta), none of the epilogue operands, K < G so the row pointers sit in the lanes.
 // The generic instantiation carried the whole epilogue's registers for it (109 VGPRs, 4 waves per SIMD) and a load of the
@@ -101,13 +111,16 @@ agg_fwd_kernel(const FwdParams p) {
     const int D = p.D;
     const float* thp = p.theta;
     const float* ptp = p.ptab;
+    // theta and the peripheral dictionary ride along behind the code tables (TAB == 1): the per-hop epilogue then has no
+    // dependent global load.  FAST reads them through these two pointers alone, so its reads are LDS reads the compiler
+    // can wait for on lgkmcnt; a pointer chosen at run time between LDS and global is a flat one, and a flat load is
+    // waited for with vmcnt(0) AND lgkmcnt(0) - it drained the next hop's prefetched rows on every hop.
+    float* const th_l = lds_tab + (((p.n_code0 + p.n_codek) * D + 3) & ~3);
+    float* const pt_l = th_l + ((p.lds_theta + 3) & ~3);
     if (TAB == 1) {
         const int n0 = p.n_code0 * D, nk = p.n_codek * D;
         for (int t = threadIdx.x; t < n0; t += kBlock) lds_tab[t] = p.table0[t];
         for (int t = threadIdx.x; t < nk; t += kBlock) lds_tab[n0 + t] = p.tablek[t];
-        // theta and the peripheral dictionary ride along: the per-hop epilogue then has no dependent global load
-        float* th_l = lds_tab + ((n0 + nk + 3) & ~3);
-        float* pt_l = th_l + ((p.lds_theta + 3) & ~3);
         if (p.alphas) {
             // theta[k,d] = softmax_k(a (1-a)^k), a = sigmoid(alphas[d]) (combine.py:43-50): K*D values, rebuilt by every
             // block instead of a launch of their own; block 0 publishes them for the backward
@@ -131,8 +144,8 @@ agg_fwd_kernel(const FwdParams p) {
         } else
         for (int t = threadIdx.x; t < p.lds_theta; t += kBlock) th_l[t] = p.theta[t];
         for (int t = threadIdx.x; t < p.lds_ptab; t += kBlock) pt_l[t] = p.ptab[t];
-        if (p.lds_theta) thp = th_l;
-        if (p.lds_ptab) ptp = pt_l;
+        if (!FAST && p.lds_theta) thp = th_l;
+        if (!FAST && p.lds_ptab) ptp = pt_l;
         __syncthreads();
     }
     const float* tab0 = TAB == 1 ? lds_tab : p.table0;
@@ -151,6 +164,14 @@ agg_fwd_kernel(const FwdParams p) {
     const uint32_t xrow_b = (uint32_t)p.x_sn * XB, trow_b = (uint32_t)D * 4u;   // (host: N * x_sn * 4 < 2^32)
     const uint32_t lane_b = col_ok ? (uint32_t)c0 * 4u : 0u;   // idle lanes re-read column 0 and are dropped below
     const uint32_t lane_bx = col_ok ? (uint32_t)c0 * XB : 0u;
+    // FAST: this thread's LDS slot for the dictionary row of the hop it is summing, behind the side tables (see pdn below)
+    typedef float park_t __attribute__((ext_vector_type(VEC)));
+    // (an LDS-typed pointer: the compiler does not infer the address space of a volatile access, and a volatile flat one is
+    //  system-scope with a vmcnt(0) behind it)
+    typedef __attribute__((address_space(3))) volatile park_t lds_park_t;
+    lds_park_t* const pk_l = (lds_park_t*)(pt_l + ((p.lds_ptab + 3) & ~3)) + threadIdx.x;
+    auto park_store = [&](const V<VEC>& v) { park_t t; for (int q = 0; q < VEC; ++q) t[q] = v.v[q]; *pk_l = t; };
+    auto park_load = [&]() { const park_t t = *pk_l; V<VEC> r; for (int q = 0; q < VEC; ++q) r.v[q] = t[q]; return r; };
 
     int last_u = -1;                        // dictionary row held in registers
     V<VEC> prow = V<VEC>::zero();
@@ -167,11 +188,17 @@ agg_fwd_kernel(const FwdParams p) {
         // DEPENDENT round trips (row pointer -> pair list -> neighbour rows, then uid -> dictionary row).  So the node's
         // K+1 row pointers, its K dictionary ids and its whole pair list (all hops, one chunk of G pairs at a time -
         // a ZINC node has ~21) are fetched up front by the lanes of the sub-group and handed out with ds_bpermute.
-        const bool lane_meta = PULL ? true : G > p.K;      // K+1 row pointers fit the sub-group's lanes (PULL: the host checked)
+        const bool lane_meta = (PULL || FAST) ? true : G > p.K;    // K+1 row pointers fit the sub-group's lanes (PULL, FAST: the host checked)
         int myrp = 0, myuid = 0;
         if (lane_meta) {
-            myrp = rp[sl <= p.K ? sl : p.K];
-            if (!PULL && (FAST || (p.uid && !p.periph))) myuid = p.uid[i * p.uid_stride + (sl < p.K ? sl : 0)];
+            // (FAST: the host checked that every byte offset of this launch fits 32 bits - see at_byte)
+            if (FAST) {
+                myrp = *at_byte(p.rowptr, ((uint32_t)i * (uint32_t)p.K_csr + (uint32_t)(sl <= p.K ? sl : p.K)) * 4u);
+                myuid = *at_byte(p.uid, ((uint32_t)i * (uint32_t)p.uid_stride + (uint32_t)(sl < p.K ? sl : 0)) * 4u);
+            } else {
+                myrp = rp[sl <= p.K ? sl : p.K];
+                if (!PULL && p.uid && !p.periph) myuid = p.uid[i * p.uid_stride + (sl < p.K ? sl : 0)];
+            }
         }
         int beg = lane_meta ? __shfl(myrp, sg_lane0) : rp[0];
         const int end_all = lane_meta ? __shfl(myrp, sg_lane0 + p.K) : rp[p.K];
@@ -181,8 +208,9 @@ agg_fwd_kernel(const FwdParams p) {
         if (!GCN) {
             const int idx = cbase + sl;
             if (idx < end_all) {
-                coff = (uint32_t)p.col[idx] * xrow_b;
-                if (TAB != 0) ctab = (uint32_t)p.code[idx] * trow_b;
+                const uint32_t cj = (uint32_t)p.col[idx], cc = TAB != 0 ? (uint32_t)p.code[idx] : 0u;   // (both requested, then both used)
+                coff = cj * xrow_b;
+                if (TAB != 0) ctab = cc * trow_b;
             }
         }
         // Rows of the NEXT hop's first pairs are requested before the current hop is summed and finished, so the one
@@ -191,10 +219,23 @@ agg_fwd_kernel(const FwdParams p) {
         V<VEC> pr[PF];
         uint32_t prb[PF];
         int prn = 0;
+        // FAST: as in agg_bwd_kernel (see the comment on gfx9's one vector-memory counter there), nothing of the hop epilogue
+        // may put a global round trip behind the wait for the prefetched rows.  The dictionary row of hop kk is requested
+        // ahead of hop kk's rows (pdn: older than they are, so the wait that consumes them covers it); after that wait it is
+        // parked in the thread's own LDS slot until the end of the hop, which frees pdn for the next request - held in a
+        // second set of registers the compiler places the hand-over copy at the loop latch, behind a vmcnt(0) that drains the
+        // rows just requested (and the two sets do not fit 5 waves per SIMD).  The slot is volatile so that the value is
+        // not forwarded in registers after all.  The S row of a hop (pend) is stored after the NEXT hop's wait, together
+        // with the requests that follow it.
+        V<VEC> pdn = V<VEC>::zero(), pend = V<VEC>::zero();
         auto prefetch = [&](int kk, int bpos, int bend) {
             prn = min(PF, min(bend, cbase + G) - bpos);
             if (prn < 0) prn = 0;
             const char* xb = reinterpret_cast<const char*>(!PULL && p.x ? p.x + (int64_t)kk * p.x_sk : p.xs[kk]);
+            if (FAST) {      // (idle lanes re-read column 0, as for the rows)
+                const int u = __shfl(myuid, sg_lane0 + kk);
+                pdn = V<VEC>::load(at_byte(p.ptab, (uint32_t)u * trow_b + lane_b));
+            }
 #pragma unroll
             for (int u = 0; u < PF; ++u) {
                 if (u < prn) {
@@ -204,6 +245,14 @@ agg_fwd_kernel(const FwdParams p) {
                     pr[u] = V<VEC>::template load_row<BF>(xb + (size_t)(o + lane_bx));
                 }
             }
+        };
+        auto store_pre = [&](int kk, const V<VEC>& v) {         // S[i, kk, :] (streaming: nobody re-reads it in this launch)
+            if (FAST) {
+                const uint32_t o = ((uint32_t)i * (uint32_t)p.K + (uint32_t)kk) * ((uint32_t)D * XB) + lane_bx;
+                if (BF) st_bf16_stream<VEC>(at_byte(p.pre, o), v.v);
+                else v.store_stream(at_byte(p.pre, o));
+            } else if (BF) st_bf16_stream<VEC>(reinterpret_cast<uint16_t*>(p.pre) + (i * p.K + kk) * (int64_t)D + c0, v.v);
+            else v.store_stream(p.pre + (i * p.K + kk) * (int64_t)D + c0);
         };
         int end_next = lane_meta ? __shfl(myrp, sg_lane0 + 1) : rp[1];
         if (!GCN) prefetch(0, beg, end_next);
@@ -234,6 +283,10 @@ agg_fwd_kernel(const FwdParams p) {
                         acc.add(r);
                     }
                 }
+                if (FAST) {     // (this hop's dictionary row arrived with its rows; the previous hop's S row leaves with the next requests)
+                    park_store(pdn);
+                    if (k > 0 && col_ok) store_pre(k - 1, pend);
+                }
                 if (k + 1 < p.K) {
                     end_next = lane_meta ? __shfl(myrp, sg_lane0 + k + 2) : rp[k + 2];
                     prefetch(k + 1, end, end_next);
@@ -245,8 +298,9 @@ agg_fwd_kernel(const FwdParams p) {
                         const int idx = cbase + sl;
                         coff = 0; ctab = 0;
                         if (idx < end_all) {
-                            coff = (uint32_t)p.col[idx] * xrow_b;
-                            if (TAB != 0) ctab = (uint32_t)p.code[idx] * trow_b;
+                            const uint32_t cj = (uint32_t)p.col[idx], cc = TAB != 0 ? (uint32_t)p.code[idx] : 0u;
+                            coff = cj * xrow_b;
+                            if (TAB != 0) ctab = cc * trow_b;
                         }
                     }
                     const int lim = min(end, cbase + G) - cbase;
@@ -327,7 +381,7 @@ agg_fwd_kernel(const FwdParams p) {
             // constant row added to every x row of hops >= 1: hopk_node_path_emb(pe_attr == 0), KPGIN.py:92-94
             const bool biased = p.xbias != nullptr && k >= 1;
             V<VEC> xb = V<VEC>::zero();
-            if (biased) { xb = V<VEC>::load(p.xbias + c0); v.fma(GCN ? wacc : (float)seglen, xb); }
+            if (biased) { xb = V<VEC>::load(FAST ? at_byte(p.xbias, lane_b) : p.xbias + c0); v.fma(GCN ? wacc : (float)seglen, xb); }
             if (GCN) {
                 const float di = p.dis[i * p.K_csr + k];
                 V<VEC> self = V<VEC>::load(xk + i * p.x_sn);
@@ -336,28 +390,31 @@ agg_fwd_kernel(const FwdParams p) {
                 v.fma(di, self);                                          // last term of the edge list
                 for (int q = 0; q < VEC; ++q) v.v[q] *= di;
             }
-            if (BF) st_bf16_stream<VEC>(reinterpret_cast<uint16_t*>(p.pre) + (i * p.K + k) * (int64_t)D + c0, v.v);
-            else if (FAST || p.pre) v.store_stream(p.pre + (i * p.K + k) * (int64_t)D + c0);
+            if (FAST) pend = v;                         // (stored after the next hop's wait, or at the end of the node)
+            else if (BF || p.pre) store_pre(k, v);
             if (MODE == KPGNN_MODE_GINPLUS) { for (int q = 0; q < VEC; ++q) v.v[q] = gelu_exact(v.v[q]); }
             if (GCN) { for (int q = 0; q < VEC; ++q) v.v[q] = fmaxf(v.v[q], 0.f); }
-            if (!FAST && p.periph) v.add(V<VEC>::load(p.periph + i * p.p_sn + (int64_t)k * p.p_sk + c0));
-            else if (FAST || p.uid) {
+            if (FAST) v.add(park_load());
+            else if (p.periph) v.add(V<VEC>::load(p.periph + i * p.p_sn + (int64_t)k * p.p_sk + c0));
+            else if (p.uid) {
                 const int u = lane_meta ? uk : p.uid[i * p.uid_stride + k];
-                if (FAST) v.add(V<VEC>::load(ptp + (int64_t)u * D + c0));        // (dictionary staged in LDS: no register copy)
-                else { if (u != last_u) { prow = V<VEC>::load(ptp + (int64_t)u * D + c0); last_u = u; } v.add(prow); }  // mostly one row
+                if (u != last_u) { prow = V<VEC>::load(ptp + (int64_t)u * D + c0); last_u = u; }  // mostly one row
+                v.add(prow);
             }
             if (MODE == KPGNN_MODE_GIN) { V<VEC> xs = V<VEC>::load(xk + i * p.x_sn); xs.add(xb); v.fma(eps1, xs); }
             if (COMBINE) {
                 if (!FAST && !thp) hsum.add(v);         // (unit weights: the pull form on a row shape without a PULL instantiation)
                 else {
-                    const V<VEC> th = V<VEC>::load(thp + k * D + c0);
+                    const V<VEC> th = V<VEC>::load((FAST ? th_l : thp) + k * D + c0);
                     for (int q = 0; q < VEC; ++q) hsum.v[q] = fmaf(th.v[q], v.v[q], hsum.v[q]);
                 }
             } else {
                 v.store_stream(p.out + i * p.o_sn + (int64_t)k * p.o_sk + c0);
             }
         }
-        if (COMBINE && col_ok) hsum.store_stream(p.hout + i * (int64_t)D + c0);
+        if (FAST && col_ok) store_pre(p.K - 1, pend);  // the last hop's S row: overlaps the next node's metadata loads
+        if (FAST) { if (col_ok) hsum.store_stream(at_byte(p.hout, (uint32_t)i * trow_b + lane_b)); }
+        else if (COMBINE && col_ok) hsum.store_stream(p.hout + i * (int64_t)D + c0);
     }
 }
 
@@ -602,13 +659,20 @@ int launch_fwd(const FwdParams& p, size_t lds, hipStream_t s) {
     return KPGNN_OK;
 }
 
+// The KP-GIN+ training epilogue: what FAST resolves at compile time, and the only one with bf16 rows.
+bool fast_epilogue(const FwdParams& p, int tab) {
+    return tab == 1 && p.mode == KPGNN_MODE_GINPLUS && p.combine && !p.periph && p.uid && p.ptab && p.pre;
+}
+// (Whether the FAST instantiation runs is decided ONCE, by kpgnn_aggregate_fwd where it sizes the LDS: p.fast.)
+
 template <int VEC, int G>
 int launch_fwd_mode(const FwdParams& p, int tab, size_t lds, hipStream_t s) {
     const bool gcn = p.mode == KPGNN_MODE_GCN;
-    const bool fast = tab == 1 && p.mode == KPGNN_MODE_GINPLUS && p.combine && !p.periph && p.uid && p.ptab && p.pre;
-    if (p.bf) {     // bf16 rows: one instantiation family only (the KP-GIN+ training epilogue, 4 elements per lane)
+    const bool fast = p.fast != 0;
+    if (p.bf) {     // bf16 rows: the KP-GIN+ training epilogue only, 4 elements per lane
         if constexpr (VEC == 4) {
             if (fast && !p.x) return launch_fwd<VEC, G, false, 1, true, true>(p, lds, s);
+            if (fast_epilogue(p, tab) && !p.x) return launch_fwd<VEC, G, false, 1, false, true>(p, lds, s);
         }
         return fail(KPGNN_EINVAL, "aggregate_fwd: bf16 storage needs the fused KP-GIN+ epilogue (GELU, theta, dictionary P, "
                     "code tables in LDS, S saved), per-hop inputs and D %% 4 == 0");
@@ -704,15 +768,10 @@ extern "C" int kpgnn_aggregate_fwd(const kpgnn_agg_fwd_desc* d, kpgnn_stream_t s
         if (rc != KPGNN_OK || handled) return rc;
     }
     FwdParams p;
-    p.lds_theta = p.lds_ptab = 0;
-    if (tab == 1) {      // small side tables behind the code tables (keeps >= 4 blocks of 256 threads per CU)
-        lds = (lds + 15) & ~(size_t)15;
-        const size_t cap = 36 * 1024;
-        const size_t th_b = combine ? sizeof(float) * (size_t)d->K * d->D : 0;
-        if (th_b && lds + th_b <= cap) { p.lds_theta = d->K * d->D; lds += (th_b + 15) & ~(size_t)15; }
-        const size_t pt_b = (!d->periph && d->ptab && d->n_dict > 0) ? sizeof(float) * (size_t)d->n_dict * d->D : 0;
-        if (pt_b && lds + pt_b <= cap) { p.lds_ptab = d->n_dict * d->D; lds += (pt_b + 15) & ~(size_t)15; }
-    }
+    p.lds_theta = p.lds_ptab = p.fast = 0;
+    const uint64_t lim32 = 1ull << 32, n64 = (uint64_t)d->N;   // every byte offset into rowptr, uid, ptab, pre and hout below 2^32?
+    const bool off32 = n64 * (uint64_t)d->K_csr * 4u < lim32 && n64 * (uint64_t)(d->uid ? d->uid_stride : 0) * 4u < lim32 &&
+                       n64 * (uint64_t)d->K * (uint64_t)d->D * 4u < lim32 && d->n_dict > 0 && (uint64_t)d->n_dict * (uint64_t)d->D * 4u < lim32;
     p.N = d->N; p.n_dyn = d->n_dyn; p.K = d->K; p.D = d->D; p.K_csr = d->K_csr; p.n_code0 = d->n_code0; p.n_codek = d->K > 1 ? d->n_codek : 0;
     p.mode = d->mode; p.combine = combine ? 1 : 0; p.bf = d->storage == KPGNN_STORE_BF16 ? 1 : 0;
     KPGNN_REQUIRE(d->storage == KPGNN_STORE_F32 || d->storage == KPGNN_STORE_BF16, "aggregate_fwd: unknown storage %d", d->storage);
@@ -722,13 +781,6 @@ extern "C" int kpgnn_aggregate_fwd(const kpgnn_agg_fwd_desc* d, kpgnn_stream_t s
     p.periph = d->periph; p.p_sn = d->p_sn; p.p_sk = d->p_sk;
     p.eps = d->eps; p.out = d->out; p.o_sn = d->o_sn; p.o_sk = d->o_sk; p.pre = d->pre; p.theta = d->theta; p.hout = d->hout; p.hinit = d->hinit; p.hinit2 = d->hinit2; p.xbias = d->xbias;
     p.alphas = nullptr; p.theta_out = nullptr;
-    if (d->alphas) {
-        if (p.lds_theta) { p.alphas = d->alphas; p.theta_out = const_cast<float*>(d->theta); }   // theta staged in LDS: computed there
-        else {                                                                                    // otherwise by a launch of its own
-            const int rc = geo_theta_fwd_launch(d->alphas, d->K, d->D, const_cast<float*>(d->theta), (hipStream_t)stream);
-            if (rc != KPGNN_OK) return rc;
-        }
-    }
     p.ptab = d->periph ? nullptr : d->ptab; p.uid = d->periph ? nullptr : d->uid; p.uid_stride = d->uid_stride;
     KPGNN_REQUIRE(p.uid == nullptr || (p.ptab != nullptr && p.uid_stride >= d->K), "aggregate_fwd: dictionary P needs ptab and uid_stride >= K");
     uintptr_t slot_bits = 0;            // low address bits of ALL per-hop inputs OR-ed: the least aligned one decides the vector width
@@ -744,8 +796,30 @@ extern "C" int kpgnn_aggregate_fwd(const kpgnn_agg_fwd_desc* d, kpgnn_stream_t s
                               d->out ? d->o_sn : 0, d->out ? d->o_sk : 0});
     const int lanes = (d->D + vec - 1) / vec;
     if (lanes > 64) return fail(KPGNN_ELIMIT, "aggregate_fwd: D=%d with %d-wide access needs %d lanes > 64", d->D, vec, lanes);
+    const int g = row_lanes(d->D, vec);
+    if (tab == 1) {      // small side tables behind the code tables (keeps >= 4 blocks of 256 threads per CU)
+        lds = (lds + 15) & ~(size_t)15;
+        const size_t cap = 36 * 1024;
+        const size_t th_b = combine ? sizeof(float) * (size_t)d->K * d->D : 0;
+        if (th_b && lds + th_b <= cap) { p.lds_theta = d->K * d->D; lds += (th_b + 15) & ~(size_t)15; }
+        // The FAST instantiation (launch_fwd_mode) needs, besides its epilogue: theta staged, the node's K + 1 row pointers and
+        // K dictionary ids in the g lanes of its sub-group, and 32-bit byte offsets.  It requests a hop's dictionary row from
+        // global memory one hop ahead (any n_dict) and parks it in one LDS slot per thread; everything else runs the generic
+        // instantiation (same sums) with the dictionary staged when it fits.
+        p.fast = fast_epilogue(p, tab) && p.lds_theta != 0 && g > p.K && off32;
+        const size_t pt_b = (!d->periph && d->ptab && d->n_dict > 0) ? sizeof(float) * (size_t)d->n_dict * d->D : 0;
+        if (p.fast) lds += (size_t)kBlock * vec * sizeof(float);
+        else if (pt_b && lds + pt_b <= cap) { p.lds_ptab = d->n_dict * d->D; lds += (pt_b + 15) & ~(size_t)15; }
+    }
     hipStream_t s = (hipStream_t)stream;
-    return dispatch_row_shape<64>(vec, row_lanes(d->D, vec), "aggregate_fwd",
+    if (d->alphas) {
+        if (p.lds_theta) { p.alphas = d->alphas; p.theta_out = const_cast<float*>(d->theta); }   // theta staged in LDS: computed there
+        else {                                                                                    // otherwise by a launch of its own
+            const int rc = geo_theta_fwd_launch(d->alphas, d->K, d->D, const_cast<float*>(d->theta), s);
+            if (rc != KPGNN_OK) return rc;
+        }
+    }
+    return dispatch_row_shape<64>(vec, g, "aggregate_fwd",
                                   [&](auto VV, auto G) { return launch_fwd_mode<VV.value, G.value>(p, tab, lds, s); });
 }
 
