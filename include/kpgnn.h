@@ -435,6 +435,11 @@ size_t kpgnn_table_grad_fuse_workspace_bytes(int32_t K, int32_t D);
  * same ids on every step (aten embedding_dense_backward under models/GNNs.py:172-179). */
 int kpgnn_dict_tile_pack(const int32_t* uid, int64_t uid_stride, int32_t N, int32_t K, int32_t nodes_per_tile,
                          uint32_t* pack, kpgnn_stream_t stream);
+/* The same under a dynamic row count: N is the capacity (the list still has ceil(N/npt) tiles), n_dyn the device-side live
+ * count (NULL: N); the places of nodes >= *n_dyn hold 0xFFFFFFFF.  kpgnn_table_grad's walk takes every entry of a list, and
+ * loads only the live rows of a tile: a list for a dynamic-row launch MUST come from this entry point with the same n_dyn. */
+int kpgnn_dict_tile_pack_dyn(const int32_t* uid, int64_t uid_stride, int32_t N, const int32_t* n_dyn, int32_t K,
+                             int32_t nodes_per_tile, uint32_t* pack, kpgnn_stream_t stream);
 
 /* Peripheral-dictionary gradient under the fused geometric combine, from gh alone (no [N,K,D] operand):
  *   gdict[u,:] = sum_k theta[k,:] * sum over nodes i with uid[i,k] == u of gh[i,:]

@@ -761,8 +761,12 @@ inline size_t tg_fuse_mfma_lds(int D, int f_U) {
 
 // Dictionary entries of every tile, sorted by dictionary row: pack[tile*64 + j] = uid << 8 | node_in_tile << 3 | hop.
 // One wave per tile; 64 keys are ranked by counting (a one-off per batch: the ids are data, not parameters).
+// n_dyn: the list covers the tiles of the capacity N and holds the LIVE nodes' entries only - the walk of kpgnn_table_grad takes
+// every entry it finds, and loads the live part of a tile only: an entry of a dead node would point at rows it never loaded.
 __global__ void __launch_bounds__(kWave)
-dict_tile_pack_kernel(const int32_t* __restrict__ uid, int64_t uid_stride, int N, int K, int NT, uint32_t* __restrict__ pack) {
+dict_tile_pack_kernel(const int32_t* __restrict__ uid, int64_t uid_stride, int N, const int32_t* __restrict__ n_dyn, int K, int NT,
+                      uint32_t* __restrict__ pack) {
+    N = live_rows(N, n_dyn);
     const int lane = threadIdx.x;
     const int64_t tl = blockIdx.x;
     const int n = lane / K, k = lane - n * K;
@@ -990,13 +994,18 @@ extern "C" size_t kpgnn_table_grad_fuse_workspace_bytes(int32_t K, int32_t D) {
 
 extern "C" int kpgnn_dict_tile_pack(const int32_t* uid, int64_t uid_stride, int32_t N, int32_t K, int32_t nodes_per_tile,
                                     uint32_t* pack, kpgnn_stream_t stream) {
+    return kpgnn_dict_tile_pack_dyn(uid, uid_stride, N, nullptr, K, nodes_per_tile, pack, stream);
+}
+
+extern "C" int kpgnn_dict_tile_pack_dyn(const int32_t* uid, int64_t uid_stride, int32_t N, const int32_t* n_dyn, int32_t K,
+                                        int32_t nodes_per_tile, uint32_t* pack, kpgnn_stream_t stream) {
     KPGNN_REQUIRE(N >= 0 && K >= 1 && K <= 8 && nodes_per_tile >= 1 && nodes_per_tile <= 8 && nodes_per_tile * K <= kMaxRows,
                   "dict_tile_pack: bad N=%d K=%d nodes_per_tile=%d (tiles of at most 8 nodes x 8 hops)", N, K, nodes_per_tile);
     if (N == 0) return KPGNN_OK;
     KPGNN_REQUIRE(uid && pack && uid_stride >= K, "dict_tile_pack: NULL uid/pack or uid_stride < K");
     const int64_t tiles = ((int64_t)N + nodes_per_tile - 1) / nodes_per_tile;
     hipLaunchKernelGGL(dict_tile_pack_kernel, dim3((unsigned)tiles), dim3(kWave), 0, (hipStream_t)stream, uid, uid_stride,
-                       N, K, nodes_per_tile, pack);
+                       N, n_dyn, K, nodes_per_tile, pack);
     KPGNN_LAUNCH_CHECK("dict_tile_pack_kernel");
     return KPGNN_OK;
 }

@@ -374,15 +374,17 @@ def dict_tile_pack(csr, uid):
     if uid.stride(1) != 1 or kf > 8 or kf < uid.shape[1] or csr.nodes_per_tile * kf > 64:
         return None, 0
     cache = csr._dict_packs
-    key = (uid.data_ptr(), kf, uid.shape[0])
-    hit = cache.get(key)
+    N = uid.shape[0]
+    dyn = dyn_ptr(N)
     # (a StaticBatch refills `uid` in place: under dynamic_rows the list is rebuilt by every call - into the same buffer, so a
-    #  captured graph refreshes it at every replay)
-    if hit is None or dyn_ptr(uid.shape[0]) is not None:
-        N = uid.shape[0]
+    #  captured graph refreshes it at every replay - and holds the live nodes' entries only: the walk takes every entry it finds.
+    #  Such a list is kept under a key of its own: a launch over all N rows of the same csr and uid never walks it.)
+    key = (uid.data_ptr(), kf, N, dyn)
+    hit = cache.get(key)
+    if hit is None or dyn is not None:
         tiles = (N + csr.nodes_per_tile - 1) // csr.nodes_per_tile
         pack = hit[0] if hit is not None else torch.empty((tiles, 64), dtype=torch.int32, device=uid.device)
-        _lib.launch("kpgnn_dict_tile_pack", uid.device, uid.data_ptr(), kf, N, kf, csr.nodes_per_tile, pack.data_ptr())
+        _lib.launch("kpgnn_dict_tile_pack_dyn", uid.device, uid.data_ptr(), kf, N, dyn, kf, csr.nodes_per_tile, pack.data_ptr())
         hit = cache[key] = (pack, kf, uid)     # (uid kept alive: the key is its address)
     return hit[0], hit[1]
 

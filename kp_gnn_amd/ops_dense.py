@@ -14,16 +14,19 @@ from .ops import _ptr, dyn_ptr, refuse_dynamic_rows
 
 # ------------------------------------------------------------------------------------------- column-statistics slots
 STAT_REPLICAS = 8          # KPGNN_STAT_REPLICAS (include/kpgnn.h)
-_EAGER_DOUBLES = 1 << 20   # 8 MB of slots between two zero fills when launching eagerly
+_EAGER_DOUBLES = 1 << 20   # 8 MB of slots, handed out in two halves of 4 MB, when launching eagerly
 _GRAPH_DOUBLES = 1 << 18   # 2 MB per captured graph (zero-filled by a node of the graph itself at every replay)
 
 
 class _Arena:
-    __slots__ = ("buf", "off")
+    """Two halves.  Slots are handed out from one half until it is used up; the arena then moves to the OTHER half and zero-fills
+    that one.  A slot is therefore zero when it is handed out and is not touched by a fill while its operator still uses it:
+    an operator takes all its slots before its first launch, so some of them may come from the half that was just left."""
+    __slots__ = ("buf", "off", "end")
 
     def __init__(self, n, dev):
         self.buf = torch.zeros(n, dtype=torch.float64, device=dev)
-        self.off = 0
+        self.off, self.end = 0, n // 2
 
 
 _arenas = {}   # device index -> {"eager": _Arena, "cap_id": int, "cap": _Arena}
@@ -31,12 +34,14 @@ _arenas = {}   # device index -> {"eager": _Arena, "cap_id": int, "cap": _Arena}
 
 def take_stat_slot(C, dev):
     """A zeroed column-statistics slot (double[STAT_REPLICAS][2][C], include/kpgnn.h) for ONE producer launch + ONE
-    consumer launch.  Slots come from a per-device arena and are never handed out twice between two zero fills of the
-    arena, so no per-use memset exists: eagerly the arena is re-zeroed every ~600 slots; a hipGraph capture gets an
-    arena of its own, allocated and zero-filled INSIDE the capture (the fill is a node of the graph: every replay
+    consumer launch.  Slots come from a per-device arena and are never handed out twice between two zero fills of their
+    half of the arena, so no per-use memset exists: eagerly a half is re-zeroed every ~300 slots; a hipGraph capture
+    gets an arena of its own, allocated and zero-filled INSIDE the capture (the fill is a node of the graph: every replay
     starts from zeros, and the memory lives in the graph's pool).
-    Callers take every slot of an operator before they launch its first kernel (a wrap-around fill must not land
-    between a slot's producer and its consumer)."""
+    Callers take every slot of an operator before they launch its first kernel.  The fill that makes room for a slot
+    covers only the half the arena moves TO: slots the same operator took a moment earlier lie in the half it leaves and
+    keep what their producer writes until the arena returns there (a fill of the whole arena at this point left those
+    slots dirty for the next round)."""
     lib = _lib.load()
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     st = _arenas.get(idx)
@@ -53,9 +58,11 @@ def take_stat_slot(C, dev):
             st["cap"], st["cap_id"] = _Arena(_GRAPH_DOUBLES, dev), cid.value
         a = st["cap"]
     n = (STAT_REPLICAS * 2 * C + 31) // 32 * 32
-    if a.off + n > a.buf.numel():
-        a.buf.zero_()
-        a.off = 0
+    if a.off + n > a.end:
+        half = a.buf.numel() // 2
+        a.off = half if a.end == half else 0
+        a.end = a.off + half
+        a.buf[a.off:a.end].zero_()
     v = a.buf[a.off:a.off + n]
     a.off += n
     return v

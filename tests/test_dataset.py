@@ -241,8 +241,11 @@ def _step(model, batch):
 def test_static_batch_dynamic_rows_equal_exact_shapes(Bsz):
     """A StaticBatch (capacity-shaped tensors, live node count on the device, every launch bounded by n_dyn) gives the same
     loss and gradients as the exact-shape batch of the same graphs - eagerly and from ONE captured hipGraph replayed on
-    different batches (different N, A, entry counts).  BatchNorm statistics, weight gradients, table gradients and the
-    readout all sum over rows: a single phantom row in any of them would show here."""
+    different batches (different N, A, entry counts).  This is the END-TO-END check of the mode: one model configuration,
+    three random live counts, dead rows that hold whatever the allocator handed back, a bound of 1e-4 of the gradient scale.
+    BatchNorm statistics, weight gradients, table gradients and the readout all sum over rows, and a phantom row of
+    ordinary magnitude in one of them shows here; that NO dead row is read, at live counts on the tile edges and with
+    poisoned dead rows and workspaces, is held kernel by kernel in tests/test_dynamic_rows_training.py."""
     from kp_gnn_amd.dataset import KHopDataset
     dev = torch.device("cuda:0")
     raw = molecules(400, seed0=21)

@@ -28,7 +28,28 @@ def _close(a, b, name, rtol=RTOL, atol=ATOL):
     b = b.detach().cpu().double()
     assert a.shape == b.shape, (name, a.shape, b.shape)
     scale = max(1.0, float(b.abs().max())) if b.numel() else 1.0
-    assert torch.allclose(a, b, rtol=rtol, atol=atol * scale), (name, float((a - b).abs().max()), scale)
+    ratio = float(((a - b).abs() / (atol * scale + rtol * b.abs())).max()) if b.numel() else 0.0      # largest error over its bound
+    assert torch.allclose(a, b, rtol=rtol, atol=atol * scale), (name, float((a - b).abs().max()), scale, ratio)
+    return ratio
+
+
+# The bounds of the exact-shape operator tests below, by operator and output: _close(..., **TOL[op][output]).  Their twins under
+# a dynamic row count (tests/test_dynamic_rows_training.py) hold the same outputs to the same numbers through this table.
+_T = dict(rtol=2e-4, atol=2e-5)
+TOL = {
+    "batch_norm_act": {"out": dict(atol=2e-5), "dx": dict(atol=3e-5), "dgamma": dict(atol=3e-5), "dbeta": dict(atol=3e-5),
+                       "running_mean": {}, "running_var": {}, "dres": {}},
+    "linear": {"y": _T, "dW": _T, "db": _T, "dx": _T},
+    "jk_projection": {"y": _T, "dW": _T, "db": _T, "dstate": _T},
+    "segment_pool": {"pool": {}, "pool grad": {}},
+    "table_gather_sum": {"out": {}, "gtable": dict(atol=3e-5), "gbias": dict(atol=3e-5)},
+    "aggregate": {"out": {}, "grad_x": {}, "grad_P": {}, "grad_table0": dict(atol=3e-5), "grad_tablek": dict(atol=3e-5)},
+    "table_grad": {"gtable0": _T, "gtablek": _T, "gdict": _T},
+    "dict_grad": {"gdict": dict(rtol=2e-4, atol=2e-4)},
+    "combine_table_grad": {"g": dict(rtol=1e-5, atol=1e-6), "gtheta": _T, "galphas": _T, "gtable0": _T, "gtablek": _T, "gdict": _T},
+    "fused_mlp": {"out": dict(rtol=2e-4, atol=3e-5), "dx": dict(rtol=3e-4, atol=5e-5), "dres": {}, "param_grads": (3e-4, 5e-5),
+                  "running": _T},
+}
 
 
 def _close_param_grads(params, ref_grads, name, rtol, atol):
@@ -220,11 +241,12 @@ def test_aggregate_modes_and_widths_vs_oracle(D, mode):
     m = {"gin": _lib.MODE_GIN, "ginplus": _lib.MODE_GINPLUS, "gcn": _lib.MODE_GCN, "sum": _lib.MODE_SUM}[mode]
     out = khop_aggregate(xd, csr, K, m, table0=t0d, tablek=tkd, periph=Pd, eps=eps.to(dev) if mode == "gin" else None)
     (out * w.to(dev)).sum().backward()
-    _close(out, ref, "out")
-    _close(xd.grad, xo.grad, "grad_x")
-    _close(Pd.grad, Po.grad, "grad_P")
-    _close(t0d.grad, t0o.grad, "grad_table0", atol=3e-5)
-    _close(tkd.grad, tko.grad, "grad_tablek", atol=3e-5)
+    T = TOL["aggregate"]
+    _close(out, ref, "out", **T["out"])
+    _close(xd.grad, xo.grad, "grad_x", **T["grad_x"])
+    _close(Pd.grad, Po.grad, "grad_P", **T["grad_P"])
+    _close(t0d.grad, t0o.grad, "grad_table0", **T["grad_table0"])
+    _close(tkd.grad, tko.grad, "grad_tablek", **T["grad_tablek"])
 
 
 def test_aggregate_strided_views_prefix_and_empty():
@@ -512,9 +534,10 @@ def test_table_gather_sum_vs_torch(D, R_sizes, M):
     td, bd = table.clone().to(dev).requires_grad_(True), bias.clone().to(dev).requires_grad_(True)
     out = table_gather_sum(td, bd, idx.to(torch.int16).to(dev), off.to(torch.int32).to(dev))
     (out * w.to(dev)).sum().backward()
-    _close(out, ref, "out")
-    _close(td.grad, tr.grad, "gtable", atol=3e-5)
-    _close(bd.grad, br.grad, "gbias", atol=3e-5)
+    T = TOL["table_gather_sum"]
+    _close(out, ref, "out", **T["out"])
+    _close(td.grad, tr.grad, "gtable", **T["gtable"])
+    _close(bd.grad, br.grad, "gbias", **T["gbias"])
 
 
 def test_aggregate_bwd_accumulating_slots_and_alias_rejection():
@@ -642,15 +665,16 @@ def test_batch_norm_act_vs_torch(N, C, relu, res):
     rd = r.clone().to(dev).requires_grad_(True) if res else None
     outd = batch_norm_act(xd, bn_hip, relu=relu, residual=rd)
     (outd * w.to(dev)).sum().backward()
-    _close(outd, out, "out", atol=2e-5)
-    _close(xd.grad, xr.grad, "dx", atol=3e-5)
-    _close(bn_hip.weight.grad, bn_ref.weight.grad, "dgamma", atol=3e-5)
-    _close(bn_hip.bias.grad, bn_ref.bias.grad, "dbeta", atol=3e-5)
-    _close(bn_hip.running_mean, bn_ref.running_mean, "running_mean")
-    _close(bn_hip.running_var, bn_ref.running_var, "running_var")
+    T = TOL["batch_norm_act"]
+    _close(outd, out, "out", **T["out"])
+    _close(xd.grad, xr.grad, "dx", **T["dx"])
+    _close(bn_hip.weight.grad, bn_ref.weight.grad, "dgamma", **T["dgamma"])
+    _close(bn_hip.bias.grad, bn_ref.bias.grad, "dbeta", **T["dbeta"])
+    _close(bn_hip.running_mean, bn_ref.running_mean, "running_mean", **T["running_mean"])
+    _close(bn_hip.running_var, bn_ref.running_var, "running_var", **T["running_var"])
     assert int(bn_hip.num_batches_tracked) == 1
     if res:
-        _close(rd.grad, rr.grad, "dres")
+        _close(rd.grad, rr.grad, "dres", **T["dres"])
 
 
 @pytest.mark.parametrize("N,O,I", [(4099, 104, 104), (1500, 33, 40), (2048, 256, 256), (1025, 1, 7), (3000, 96, 13)])
@@ -668,13 +692,14 @@ def test_linear_wgrad_mfma_vs_torch(N, O, I):
     xd, wd, bd = (t.clone().to(dev).requires_grad_(True) for t in (x, w, b))
     out = LinearWgrad.apply(xd, wd, bd)
     (out * gy.to(dev)).sum().backward()
-    _close(wd.grad, wr.grad, "dW", rtol=2e-4, atol=2e-5)
-    _close(bd.grad, br.grad, "db", rtol=2e-4, atol=2e-5)
-    _close(xd.grad, xr.grad, "dx", rtol=2e-4, atol=2e-5)
+    T = TOL["linear"]
+    _close(wd.grad, wr.grad, "dW", **T["dW"])
+    _close(bd.grad, br.grad, "db", **T["db"])
+    _close(xd.grad, xr.grad, "dx", **T["dx"])
     # without bias
     wd2 = w.clone().to(dev).requires_grad_(True)
     (LinearWgrad.apply(x.to(dev), wd2, None) * gy.to(dev)).sum().backward()
-    _close(wd2.grad, wr.grad, "dW (no bias)", rtol=2e-4, atol=2e-5)
+    _close(wd2.grad, wr.grad, "dW (no bias)", **T["dW"])
 
 
 def test_linear_wgrad_pair_and_x_transform():
@@ -734,13 +759,14 @@ def test_jk_projection_native_vs_torch(N, H, S, O):
     sr = [t.clone().requires_grad_(True) for t in states]
     wr, br = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
     pre = torch.nn.functional.linear(torch.cat(sr, dim=1), wr, br)
-    _close(y, torch.relu(pre.detach()), "y", rtol=2e-4, atol=2e-5)
+    T = TOL["jk_projection"]
+    _close(y, torch.relu(pre.detach()), "y", **T["y"])
     mask = (y.detach().cpu() > 0).to(pre.dtype)
     ((pre * mask) * gy).sum().backward()
-    _close(wd.grad, wr.grad, "dW", rtol=2e-4, atol=2e-5)
-    _close(bd.grad, br.grad, "db", rtol=2e-4, atol=2e-5)
+    _close(wd.grad, wr.grad, "dW", **T["dW"])
+    _close(bd.grad, br.grad, "db", **T["db"])
     for l in range(S):
-        _close(sd[l].grad, sr[l].grad, f"dstate{l}", rtol=2e-4, atol=2e-5)
+        _close(sd[l].grad, sr[l].grad, f"dstate{l}", **T["dstate"])
     # without bias, and a second call gives the same bits (fixed summation order)
     wd2 = w.clone().to(dev).requires_grad_(True)
     y2 = JKConcatLinear.apply(wd2, None, *[t.detach() for t in sd])
@@ -965,8 +991,8 @@ def test_mfma_linear_forward_kernel(N, O, I):
     y = ops_dense._mfma_linear(x.to(dev), w.to(dev), b.to(dev))
     dx = ops_dense._mfma_linear(dy.to(dev), wd.to(dev), None, transposed=True)
     assert y is not None and dx is not None
-    _close(y, torch.nn.functional.linear(x, w, b), "y", rtol=2e-4, atol=2e-5)
-    _close(dx, dy @ wd, "dx", rtol=2e-4, atol=2e-5)
+    _close(y, torch.nn.functional.linear(x, w, b), "y", **TOL["linear"]["y"])
+    _close(dx, dy @ wd, "dx", **TOL["linear"]["dx"])
 
 
 @pytest.mark.parametrize("N,K,DI,DO", [(1000, 8, 13, 13), (77, 6, 20, 20), (4099, 16, 6, 6), (130, 3, 5, 9),
@@ -1071,12 +1097,13 @@ def test_table_grad_kernels_agree_with_index_add(kernel, D, dict_mode):
     code = ea[e, k]
     ref0 = torch.zeros(6, D).index_add_(0, code[k == 0], rows[k == 0])
     refk = torch.zeros(6, D).index_add_(0, code[k > 0], rows[k > 0])
-    _close(gt0, ref0, "gtable0", rtol=2e-4, atol=2e-5)
-    _close(gtk, refk, "gtablek", rtol=2e-4, atol=2e-5)
+    T = TOL["table_grad"]
+    _close(gt0, ref0, "gtable0", **T["gtable0"])
+    _close(gtk, refk, "gtablek", **T["gtablek"])
     if dict_mode != "none":
         src = (theta.unsqueeze(0) * gh.unsqueeze(1)) if dict_mode == "theta_gh" else gt
         refd = torch.zeros(U, D).index_add_(0, uid.reshape(-1).long(), src.reshape(-1, D))
-        _close(gd, refd, "gdict", rtol=2e-4, atol=2e-5)
+        _close(gd, refd, "gdict", **T["gdict"])
 
 
 @pytest.mark.parametrize("k_act", [1, 3, 8])
@@ -1138,7 +1165,7 @@ def test_dict_grad_matches_index_add_bitwise(N, k_act, D, U):
     b = ops.dict_grad_raw(uid, U, theta.to(dev), gh.to(dev))
     assert a is not None and torch.equal(a, b)
     ref = torch.zeros(U, D).index_add_(0, uid.cpu().reshape(-1).long(), (theta.unsqueeze(0) * gh.unsqueeze(1)).reshape(-1, D))
-    _close(a, ref, "gdict", rtol=2e-4, atol=2e-4)
+    _close(a, ref, "gdict", **TOL["dict_grad"]["gdict"])
     # with a designated id per hop (total minus the rest): the most frequent id, an arbitrary one, an out-of-range one
     for dom in (torch.mode(uid, dim=0).values, torch.full((k_act,), U - 1), torch.full((k_act,), U + 5)):
         uid_h = uid_full[:, :k_act]
@@ -1146,7 +1173,7 @@ def test_dict_grad_matches_index_add_bitwise(N, k_act, D, U):
         c = ops.dict_grad_raw(uid_h, U, theta.to(dev), gh.to(dev))
         c2 = ops.dict_grad_raw(uid_h, U, theta.to(dev), gh.to(dev))
         assert torch.equal(c, c2)
-        _close(c, ref, "gdict (designated id)", rtol=2e-4, atol=2e-4)
+        _close(c, ref, "gdict (designated id)", **TOL["dict_grad"]["gdict"])
     assert ops.dict_grad_raw(uid, 4000, theta.to(dev), gh.to(dev)) is None      # does not fit LDS: the caller falls back
 
 
@@ -1193,14 +1220,15 @@ def test_fused_combine_table_grad_matches_separate_kernels(N, k_act, D, in_walk)
         assert 1 <= csr.max_multiplicity() < 64       # (the condition of the matrix-core kernel: it is the one that ran)
     for a, b in zip(r[:1] + (r[1][0], r[1][1]) + r[2:], r2[:1] + (r2[1][0], r2[1][1]) + r2[2:]):
         assert (a is None) == (b is None) and (a is None or torch.equal(a, b)), "fused kernel is not bitwise repeatable"
-    _close(r[0], g_ref.cpu(), "g", rtol=1e-5, atol=1e-6)
-    _close(r[1][0], gth_ref[0].cpu(), "gtheta", rtol=2e-4, atol=2e-5)
-    _close(r[1][1], gth_ref[1].cpu(), "galphas", rtol=2e-4, atol=2e-5)
-    _close(r[2], t_ref[0].cpu(), "gtable0", rtol=2e-4, atol=2e-5)
+    T = TOL["combine_table_grad"]
+    _close(r[0], g_ref.cpu(), "g", **T["g"])
+    _close(r[1][0], gth_ref[0].cpu(), "gtheta", **T["gtheta"])
+    _close(r[1][1], gth_ref[1].cpu(), "galphas", **T["galphas"])
+    _close(r[2], t_ref[0].cpu(), "gtable0", **T["gtable0"])
     if k_act > 1:
-        _close(r[3], t_ref[1].cpu(), "gtablek", rtol=2e-4, atol=2e-5)
+        _close(r[3], t_ref[1].cpu(), "gtablek", **T["gtablek"])
     if in_walk:
-        _close(r[4], t_ref[2].cpu(), "gdict", rtol=2e-4, atol=2e-5)
+        _close(r[4], t_ref[2].cpu(), "gdict", **T["gdict"])
 
 
 @pytest.mark.parametrize("nk", [12, 1002])
@@ -1365,7 +1393,7 @@ def test_fused_mlp_vs_torch_f32(N, I, O, follow_norm):
         ops_dense.set_dense_math("auto")
 
 
-def _fused_mlp_case(N, I, O, follow_norm):
+def _fused_mlp_case(N, I, O, follow_norm, live=None, poison=float("nan"), scope=None):
     """kpgnn_linear_bn + slots: Linear-BN-ReLU-Linear-BN-ReLU (KPGINplus.py:25-30) in 3 + 5 launches against the same
     sequence of torch ops on the CPU in FLOAT64 (training mode; an fp32 CPU batch_norm is itself 4e-4 .. 8e-3 of the gradient
     scale away from float64 at 4096 x 128 x 128, depending on its thread count): output, running statistics, the input gradient
@@ -1376,7 +1404,12 @@ def _fused_mlp_case(N, I, O, follow_norm):
     With millions of elements a few pre-activations land within rounding of the ReLU kink, where the reference's and
     our mean / invstd (different summation order) decide the sign differently and a whole row of the backward differs
     legitimately: the CPU side therefore applies the ReLUs as multiplications by the masks the GPU forward used (rebuilt
-    bit-exactly from its saved tensors) - same function, same gradient, no kink ambiguity."""
+    bit-exactly from its saved tensors) - same function, same gradient, no kink ambiguity.
+    live (tests/test_dynamic_rows_training.py): N is a capacity - rows >= live of x, the residual, the upstream gradient and the
+    parked cell share hold `poison`, forward and backward run inside `scope()` (that file's dynamic_rows block) and the float64
+    reference sees rows < live only.  Same comparisons, same numbers; returns what the caller checks further (dead rows, the
+    two poisons against each other)."""
+    import contextlib
     import copy
     import torch.nn.functional as F
     from kp_gnn_amd.ops_dense import FusedMLP, batch_norm_act, mlp_linear_bn_relu_x2
@@ -1394,28 +1427,37 @@ def _fused_mlp_case(N, I, O, follow_norm):
     x = torch.randn(N, I, generator=g) * (1 + 0.02 * torch.arange(I)) + 0.5
     res = torch.randn(N, O, generator=g)
     w = torch.randn(N, O, generator=g)
+    L = N if live is None else live
+    if live is not None:
+        for t in (x, res, w):
+            t[L:] = poison
     xd, rd = x.to(dev).requires_grad_(True), res.to(dev).requires_grad_(True)
     cell = None
     if follow_norm == "fused_cell":
         from kp_gnn_amd import ops
         cell = ops.state_cell(rd)
     post = (norm_hip, rd) if follow_norm in ("fused", "fused_cell") else None
-    outd = mlp_linear_bn_relu_x2(hip, xd, emit_out_stats=bool(follow_norm), post_norm=post)
-    node = outd.grad_fn
-    assert isinstance(node, FusedMLP._backward_cls)              # the fused path ran
-    m1, m2 = _gpu_relu_masks(node)
-    if follow_norm is True:
-        from kp_gnn_amd import ops_dense
-        assert ops_dense._column_stats_of(outd) is not None      # ... and left its statistics for the next BatchNorm
-        outd = batch_norm_act(outd, norm_hip, relu=False, residual=rd)
-    if cell is not None:
-        # a later reader's share, parked DURING the backward pass, before this node runs (a share parked by another pass - or
-        # outside one - counts as stale: ops._SlotGradCell)
-        def park(gr):
-            cell.buf = torch.full((N, O), 0.25, device=dev)
-            return gr
-        outd.register_hook(park)
-    (outd * w.to(dev)).sum().backward()
+    with (scope() if live is not None else contextlib.nullcontext()):
+        outd = mlp_linear_bn_relu_x2(hip, xd, emit_out_stats=bool(follow_norm), post_norm=post)
+        node = outd.grad_fn
+        assert isinstance(node, FusedMLP._backward_cls)              # the fused path ran
+        m1, m2 = (m[:L] for m in _gpu_relu_masks(node))
+        if follow_norm is True:
+            from kp_gnn_amd import ops_dense
+            assert ops_dense._column_stats_of(outd) is not None      # ... and left its statistics for the next BatchNorm
+            outd = batch_norm_act(outd, norm_hip, relu=False, residual=rd)
+        if cell is not None:
+            # a later reader's share, parked DURING the backward pass, before this node runs (a share parked by another pass - or
+            # outside one - counts as stale: ops._SlotGradCell)
+            def park(gr):
+                share = torch.full((N, O), 0.25, device=dev)
+                share[L:] = poison
+                cell.buf = share
+                return gr
+            outd.register_hook(park)
+        (outd * w.to(dev)).sum().backward()
+    got = {"out": outd.detach(), "dx": xd.grad}
+    outd, dxd, x, res, w = outd[:L], xd.grad[:L], x[:L], res[:L], w[:L]
 
     def bn(t, m):
         return F.batch_norm(t, m.running_mean, m.running_var, m.weight, m.bias, True, m.momentum, m.eps)
@@ -1427,24 +1469,40 @@ def _fused_mlp_case(N, I, O, follow_norm):
         out = bn(out, norm_ref) + rr
     assert out.dtype == torch.float64
     (out * w.double()).sum().backward()
-    _close(outd, out, "out", rtol=2e-4, atol=3e-5)
-    _close(xd.grad, xr.grad, "dx", rtol=3e-4, atol=5e-5)
+    T = TOL["fused_mlp"]
+    _close(outd, out, "out", **T["out"])
+    _close(dxd, xr.grad, "dx", **T["dx"])
     if cell is not None:
         assert rd.grad is None
         if cell._add is not None:        # (large batches: handed over as an addend of the state's pull gather, ops.pull_applies)
-            _close(cell._add + (cell._buf - 0.25), rr.grad, "dres (cell, addend)")
+            got["dres"] = cell._add + (cell._buf - 0.25)
+            _close(got["dres"][:L], rr.grad, "dres (cell, addend)", **T["dres"])
         else:
-            _close(cell._buf - 0.25, rr.grad, "dres (cell)")
+            got["dres"] = cell._buf - 0.25
+            _close(got["dres"][:L], rr.grad, "dres (cell)", **T["dres"])
+        got["dres_rows"] = cell._buf
     elif follow_norm:
-        _close(rd.grad, rr.grad, "dres")
+        got["dres"] = got["dres_rows"] = rd.grad
+        _close(rd.grad[:L], rr.grad, "dres", **T["dres"])
     pr, ph = dict(ref.named_parameters()), dict(hip.named_parameters())
     if follow_norm:
         pr.update({"norm." + k: v for k, v in norm_ref.named_parameters()})
         ph.update({"norm." + k: v for k, v in norm_hip.named_parameters()})
-    _close_param_grads(ph, {k: v.grad for k, v in pr.items()}, f"mlp{N}x{I}x{O}", 3e-4, 5e-5)
+    _close_param_grads(ph, {k: v.grad for k, v in pr.items()}, f"mlp{N}x{I}x{O}", *T["param_grads"])
     for k, v in ref.state_dict().items():
         if "running" in k:
-            _close(hip.state_dict()[k], v, k, rtol=2e-4, atol=2e-5)
+            _close(hip.state_dict()[k], v, k, **T["running"])
+        elif live is not None and "num_batches_tracked" in k:
+            assert int(hip.state_dict()[k]) == 1, k
+    if follow_norm:       # the norm behind the MLP (fused: updated by the stacked apply pass, a kernel of its own)
+        _close(norm_hip.running_mean, norm_ref.running_mean, "norm.running_mean", **T["running"])
+        _close(norm_hip.running_var, norm_ref.running_var, "norm.running_var", **T["running"])
+        assert int(norm_hip.num_batches_tracked) == 1         # (the reference side calls the functional form: no counter there)
+    got["reduced"] = {**{"grad " + k: v.grad for k, v in ph.items()},
+                      **{k: v for k, v in list(hip.state_dict().items()) + [("norm." + a, b) for a, b in norm_hip.state_dict().items()]
+                         if "running" in k or "num_batches" in k}}
+    got["ref_grads"] = {"grad " + k: v.grad for k, v in pr.items()}
+    return got
 
 
 def test_fused_mlp_falls_back_outside_its_shapes():
@@ -1494,6 +1552,33 @@ def test_stat_slots_survive_arena_wraparound_and_capture():
         assert torch.equal(first, o)
 
 
+def test_stat_slots_taken_before_an_arena_fill_are_clean_in_the_next_round():
+    """An operator that takes TWO slots before its first launch (the fused MLP's forward), repeated through three rounds of the
+    eager arena.  One odd slot is taken first, so that a fill of the arena falls between an operator's first and second slot
+    and the first one is written AFTER the fill; one more odd slot a little over a round later shifts the pairs, so that the
+    bytes of that first slot come up again as the SECOND slot of an operator - with no fill in front of its use.  They must
+    have been zeroed by then: a dirty slot adds another operator's column sums to this one's.  Every result equals the first
+    to rounding (the fp64 atomics of the statistics arrive in varying order)."""
+    from kp_gnn_amd import ops_dense
+    dev = _dev()
+    torch.manual_seed(2)
+    O = 104
+    mlp = torch.nn.Sequential(torch.nn.Linear(O, O), torch.nn.BatchNorm1d(O, track_running_stats=False), torch.nn.ReLU(),
+                              torch.nn.Linear(O, O), torch.nn.BatchNorm1d(O, track_running_stats=False), torch.nn.ReLU()).to(dev).train()
+    x = torch.randn(64, O, device=dev) + 1.0
+    per_round = ops_dense._EAGER_DOUBLES // (2 * ops_dense.STAT_REPLICAS * 2 * O)      # operators per round of the arena
+    ops_dense.take_stat_slot(O, dev)
+    first, worst = None, 0.0
+    for i in range(3 * per_round + 5):
+        if i % (per_round + 10) == per_round + 9:
+            ops_dense.take_stat_slot(O, dev)
+        out = ops_dense.mlp_linear_bn_relu_x2(mlp, x)
+        assert isinstance(out.grad_fn, ops_dense.FusedMLP._backward_cls)
+        first = out.detach().clone() if first is None else first
+        worst = max(worst, float((out.detach() - first).abs().max()))
+    assert worst <= 1e-5 * max(1.0, float(first.abs().max())), worst
+
+
 @pytest.mark.parametrize("D", [104, 13, 1, 96, 250])
 @pytest.mark.parametrize("mean", [False, True])
 def test_segment_pool_vs_index_add(D, mean):
@@ -1518,8 +1603,8 @@ def test_segment_pool_vs_index_add(D, mean):
     bd = batch.to(dev)
     out = segment_pool(xd, bd, 300, mean=mean)
     (out * w.to(dev)).sum().backward()
-    _close(out, ref, "pool")
-    _close(xd.grad, xr.grad, "pool grad")
+    _close(out, ref, "pool", **TOL["segment_pool"]["pool"])
+    _close(xd.grad, xr.grad, "pool grad", **TOL["segment_pool"]["pool grad"])
     assert torch.equal(out, segment_pool(xd, bd, 300, mean=mean))
     with pytest.raises(ValueError):
         segment_pool(xd, torch.flip(bd, [0]).contiguous(), 300)
