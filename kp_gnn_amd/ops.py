@@ -1,5 +1,6 @@
 """Autograd operators over the C ABI (include/kpgnn.h).  Host-side plumbing only: tensors in, pointers
 and strides out; every arithmetic step of the K-hop aggregation runs in the HIP kernels."""
+import collections
 import ctypes
 
 import torch
@@ -669,9 +670,15 @@ class KHopAggregate(torch.autograd.Function):
     detached constant row, see kpgnn.h) carries no gradient: it is the padding row of hopk_node_path_emb,
     whose grad the reference's nn.Embedding(padding_idx=0) discards as well.
 
-    Backward = three HIP launches: kpgnn_combine_bwd (g = dL/dS, theta grad) when the epilogue has an
-    activation or a fused combine, kpgnn_table_grad (edge-code table + dictionary grads, no atomics),
-    kpgnn_aggregate_bwd (the transposed gather for dL/dx)."""
+    Backward = five stages, each a function below the class:
+      1. epilogue    g = dL/dS, dL/dP, the theta / alphas gradient: the fused combine + table-gradient kernel (KP-GIN+ with a
+                     fused combine, dictionary P and code tables: the table gradients and this layer's dictionary share come
+                     with it), else kpgnn_combine_bwd (an activation or a fused combine), else g = dL/dout;
+      2. tables      kpgnn_dict_grad / kpgnn_table_grad for the edge-code tables and the dictionary (no atomics) - or the
+                     tables are left to the gather; skipped after the fused kernel;
+      3. dictionary  the layer's share (_DictShare) settled against the cell of a dictionary several layers read;
+      4. gather      dL/dx: the pull form (kpgnn_khop_pull_gather, one launch per state) or kpgnn_aggregate_bwd;
+      5. tails       d/dalphas through theta where no finishing launch produced it, the eps gradient."""
 
     @staticmethod
     def forward(ctx, x, table0, tablek, periph, eps, theta, xbias, ptab, csr, k_act, mode, uid, cells, *xs):
@@ -746,217 +753,299 @@ class KHopAggregate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         pre, eps, theta, periph, x_saved, xbias, ptab = ctx.saved_tensors
-        mode, csr, k_act, uid = ctx.mode, ctx.csr, ctx.k_act, ctx.uid
-        galphas_done = False
-        fused = theta is not None
-        need_act = mode in (MODE_GINPLUS, MODE_GCN)
-        want_gperiph = ctx.has_periph and ctx.needs_input_grad[3]
-        want_gdict = ctx.n_dict > 0 and ctx.needs_input_grad[7]
-        gtheta = gperiph = gdict = acc = None
-        acc_used = False
-        dict_parked = False
-        gout = gout.contiguous() if fused else _last_contig(gout)
-        want_tables = ctx.has_tables and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        gt0 = gtk = None
+        gout = gout.contiguous() if theta is not None else _last_contig(gout)
+        want_tables = ctx.has_tables and (_needs(ctx, "table0") or _needs(ctx, "tablek"))
+        want_gdict = ctx.n_dict > 0 and _needs(ctx, "ptab")
+        want_gperiph = ctx.has_periph and _needs(ctx, "periph")
+        g, gperiph, gtheta, galphas, tables, share = _epilogue_bwd(ctx, pre, theta, periph, ptab, gout,
+                                                                   want_tables, want_gdict, want_gperiph)
         tables_in_gather = False
-        done = False
-        # --- KP-GIN+ with the fused geometric combine, dictionary P and edge-code tables: ONE kernel computes dL/dS from S and
-        #     gh, writes it for the gather below and takes the table gradients from the LDS copy of each tile; the dictionary
-        #     gradient comes from gh alone (dict_grad), its partial sums added up by the same finishing launch
-        if (fused and mode == MODE_GINPLUS and want_tables and periph is None and not want_gperiph
-                and _combine_table_grad_ok(csr, pre, ctx.n_code0 + (ctx.n_codek if k_act > 1 else 0), ctx.n_dict)):
-            extra = dg = None
-            if want_gdict and ctx.dict_cell is not None and ctx.dict_cell.buf is not None:
-                acc = ctx.dict_cell.buf                       # later layers' share: the finishing launch adds to it
-            if want_gdict and pre.shape[0] >= 4096:
-                if ctx.dict_cell is not None and dict_multi_ok(uid, ctx.n_dict, theta, gout):
-                    ctx.dict_cell.park_dict(uid, theta, gout)        # ONE launch for all the layers, run by the last of them
-                    dict_parked = True
-                    acc = None
-                else:
-                    dg = dict_grad_raw(uid, ctx.n_dict, theta, gout, defer=True)
-                    extra = dg
-            in_walk = ctx.n_dict if (want_gdict and dg is None and not dict_parked) else 0   # small batches: the dictionary rows ride along
-            r = combine_table_grad_raw(csr, pre, gout, theta, ptab, uid, ctx.n_code0, ctx.n_codek,
-                                       want_gtheta=ctx.needs_input_grad[5], alphas=ctx.alphas, extra=extra, dict_rows=in_walk,
-                                       gdict_acc=acc)
-            if r is None and in_walk:
-                r = combine_table_grad_raw(csr, pre, gout, theta, ptab, uid, ctx.n_code0, ctx.n_codek,
-                                           want_gtheta=ctx.needs_input_grad[5], alphas=ctx.alphas)
-                in_walk = 0
-            if r is None and dict_parked:            # (no fused kernel for this shape after all: the share goes the plain way below)
-                ctx.dict_cell._dg.pop()
-                dict_parked = False
-            if r is not None:
-                g, gtheta, gt0, gtk = r[:4]
-                if isinstance(gtheta, tuple):
-                    gtheta = gtheta[1]
-                    galphas_done = True
-                if dg is not None:
-                    gdict = dg[0] if acc is None else acc
-                    acc = None
-                elif in_walk:
-                    gdict = r[4]
-                    acc = None
-                elif want_gdict and not dict_parked:
-                    gdict = table_grad_raw(csr, g, 0, 0, edges=False, uid=uid, n_dict=ctx.n_dict, theta=theta, gh=gout)[2]
-                done = True
-            elif dg is not None:
-                raise _lib.KpgnnError("table_grad refused a shape after dict_grad deferred its reduction to it")
-        if done:
-            pass
-        elif fused or need_act:
-            g, gv, gtheta = combine_bwd_raw(mode, pre, gout, theta, periph, ptab, uid,
-                                            want_gtheta=fused and ctx.needs_input_grad[5],
-                                            want_gv=fused and want_gperiph, alphas=ctx.alphas if fused else None)
-            if isinstance(gtheta, tuple):            # geometric combine: d/dalphas came with the same finishing launch
-                gtheta = gtheta[1]
-                galphas_done = True
-            gperiph = gv if fused else (gout if want_gperiph else None)
-        else:
-            g = gout
-            gperiph = gout if want_gperiph else None
-        # --- table gradients (edge codes + peripheral dictionary), column-private kernel
-        if not done and (want_tables or want_gdict):
-            edges_here = want_tables and mode != MODE_GCN   # GCN weights its table grads per edge: fused atomics
-            dict_here = want_gdict and (fused or not need_act)  # g == dL/dP only without an activation
-            res = None
-            extra = None
-            # (below ~4K nodes the walk's own dictionary path is cheaper than a second kernel: 1.44 vs 1.52 ms per step at
-            #  batch 64, where every launch is latency-bound)
-            if dict_here and fused and (g.shape[0] >= 4096 or not edges_here):   # from gh alone (20 MB, not [N,K,D])
-                # (its partial sums are added up by table_grad's finishing launch when one follows)
-                dg = dict_grad_raw(uid, ctx.n_dict, theta, gout, defer=edges_here)
-                if dg is not None:
-                    dict_here = False
-                    if edges_here:
-                        gdict, extra = dg[0], dg
-                    else:
-                        gdict = dg
-            if edges_here or dict_here:
-                if dict_here and ctx.dict_cell is not None and ctx.dict_cell.buf is not None:
-                    acc = ctx.dict_cell.buf          # later layers' share: this call's finishing launch adds to it
-                res = table_grad_raw(csr, g, ctx.n_code0, ctx.n_codek, edges=edges_here,
-                                     uid=uid if dict_here else None, n_dict=ctx.n_dict if dict_here else 0,
-                                     theta=theta if fused else None, gh=gout if fused else None, extra=extra,
-                                     gdict_acc=acc if dict_here else None)
-                if res is None and extra is not None:
-                    raise _lib.KpgnnError("table_grad refused a shape after dict_grad deferred its reduction to it")
-                if res is not None and dict_here and acc is not None:
-                    acc_used = True
-            if res is not None:
-                gt0, gtk = res[0], res[1]
-                gdict = res[2] if gdict is None else gdict
-            if want_tables and (res is None or not edges_here):
-                tables_in_gather = True
-            if want_gdict and gdict is None:  # activation without fused combine (or oversize tables): dL/dP = gout
-                r2 = table_grad_raw(csr, gout if not fused else (gout.unsqueeze(1) * theta.unsqueeze(0)),
-                                    0, 0, edges=False, uid=uid, n_dict=ctx.n_dict)
-                if r2 is None:
-                    raise _lib.KpgnnError("peripheral dictionary too large for the LDS table-gradient kernel; "
-                                          "pass a dense peripheral_attr instead")
-                gdict = r2[2]
-        if ctx.dict_cell is not None and want_gdict and ctx.dict_first:
-            items = ctx.dict_cell.take_dicts()       # the last reader in backward order: every parked layer's share in ONE launch
-            if items:
-                gm = dict_grad_multi_raw(items, ctx.n_dict)
-                gdict = gm if gdict is None else gdict + gm
-        if ctx.dict_cell is not None and want_gdict:
-            if dict_parked and not ctx.dict_first:
-                gdict = None                         # (this layer's share waits in the cell's list; a share in `buf` stays where it is)
-            else:
-                if acc_used:
-                    acc = None                       # (already inside gdict)
-                elif acc is None and (not done or dict_parked) and ctx.dict_cell.buf is not None:
-                    acc = ctx.dict_cell.buf
-                if acc is not None:                  # (a path without the accumulating launch: add the parked share the plain way)
-                    gdict = gdict + acc
-                if ctx.dict_first:
-                    ctx.dict_cell.buf = None         # the total goes to autograd
-                else:
-                    ctx.dict_cell.buf, gdict = gdict, None
-        xbuf = None
-        if (ctx.x_cell is not None and ctx.x_cell.buf is not None and ctx.needs_input_grad[0] and k_act <= 32
-                and mode != MODE_GCN and not tables_in_gather):
-            b = ctx.x_cell.buf
-            if b.is_contiguous() and b.numel() == g.numel() and b.dtype == torch.float32:
-                xbuf = b
-        # --- pull form (KP-GIN+ history pattern, large batches): this layer's hop slabs of g are parked with the states it read
-        #     as slots >= 1; the state it read as slot 0 - whose last reader it is - gets its WHOLE gradient from one gather over
-        #     the slabs later layers parked for it, this layer's hop-0 slab and whatever share the cell already holds
-        pull = (PULL_GATHER and ctx.n_slots > 0 and ctx.cells is not None and mode == MODE_GINPLUS and not tables_in_gather and eps is None
-                and g.dtype == torch.float32 and g.shape[0] >= 4096 and g.shape[2] % 4 == 0 and k_act <= 16
-                and all(g[:, k].is_contiguous() for k in range(k_act)))
-        if pull:
-            for k in range(1, k_act):
-                ctx.cells[k].park_slab(k, g[:, k])
-            c0 = ctx.cells[0]
-            pend = c0.take_slabs()
-            top = max(pend) if pend else 0
-            zeros = None
-            slabs = [g[:, 0]]
-            for h in range(1, top + 1):
-                t = pend.get(h)
-                if t is None:            # (a hop nobody parked - a pruned backward pass: gathered from zeros)
-                    zeros = torch.zeros_like(slabs[0]) if zeros is None else zeros
-                    t = zeros
-                slabs.append(t)
-            hb = c0.buf
-            shape = tuple(slabs[0].shape)
-            ok = lambda t: t is not None and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == shape
-            hinit = hb if ok(hb) else None
-            ext = c0.take_addend()
-            hinit2 = ext if ok(ext) else None
-            total = khop_pull_gather(csr, slabs[:16], hinit, hinit2)
-            if hb is not None and hinit is None:
-                total = total + hb.view_as(total)          # (odd layout: add the parked share the plain way)
-            if ext is not None and hinit2 is None:
-                total = total + ext.view_as(total)
-            c0.buf = None
-            return (None, gt0, gtk, gperiph, None, _finish_gtheta(ctx, gtheta, theta, galphas_done, k_act), None, gdict, None, None, None,
-                    None, None, total, *([None] * (k_act - 1)))
-        gx, a0, ak = aggregate_bwd_raw(csr, k_act, mode, g, eps, ctx.n_code0, ctx.n_codek, tables_in_gather,
-                                       slots=ctx.n_slots > 0, slot_bufs=_slot_bufs(ctx), gx_accum=xbuf)
-        if ctx.n_slots > 0 and ctx.cells is not None:
-            ext = ctx.cells[0].take_addend()      # (a share handed over for the pull form that this layer could not run)
-            if ext is not None:
-                gx = list(gx)
-                gx[0] = gx[0] + ext.view_as(gx[0])
-            pend = ctx.cells[0].take_slabs()      # (later layers ran the pull form, this one could not: their slabs for ITS slot-0 state)
-            if pend:
-                zeros = torch.zeros_like(next(iter(pend.values())))
-                extra = khop_pull_gather(csr, [pend.get(h, zeros) for h in range(0, max(pend) + 1)], None)
-                gx = list(gx)
-                gx[0] = gx[0] + extra
-        if ctx.x_cell is not None:
-            if xbuf is None and ctx.x_cell.buf is not None and ctx.needs_input_grad[0]:
-                gx = gx + ctx.x_cell.buf.view_as(gx)     # (odd layout: add the parked share the plain way)
-            ctx.x_cell.buf = None
+        if tables is None:                # (only the fused epilogue brings the table gradients and a dictionary share along)
+            tables, tables_in_gather, share = _table_stage(ctx, g, gout, theta, want_tables, want_gdict)
+        gdict = _settle_dict_share(ctx.dict_cell, ctx.dict_first, share, ctx.n_dict) if want_gdict else None
+        if _pull_form_applies(ctx, g, eps, tables_in_gather):
+            slots = [_gather_pull(ctx, g)] + [None] * (ctx.k_act - 1)
+            gtheta = _finish_gtheta(ctx, gtheta, galphas, theta)
+            return _input_grads(table0=tables[0], tablek=tables[1], periph=gperiph, theta=gtheta, ptab=gdict, slots=slots)
+        gx, gathered = _gather_push(ctx, g, eps, tables_in_gather)
         if tables_in_gather:
-            gt0, gtk = a0, ak
-        gtheta = _finish_gtheta(ctx, gtheta, theta, galphas_done, k_act)
-        geps = None
-        if eps is not None and ctx.needs_input_grad[4] and mode == MODE_GIN:
-            refuse_dynamic_rows("the eps gradient (framework sum over rows)", g.shape[0])
-            xe = x_saved
-            if xbias is not None and xe.shape[1] > 1:
-                xe = torch.cat([xe[:, :1], xe[:, 1:] + xbias], dim=1)
-            geps = (g * xe).sum().reshape(eps.shape)
+            tables = gathered
+        gtheta = _finish_gtheta(ctx, gtheta, galphas, theta)
+        geps = _eps_grad(ctx, g, eps, x_saved, xbias)
         # (row 0 of both table grads stays exactly zero: code 0 == "inactive" never enters the CSR, which
         #  is also what nn.Embedding(padding_idx=0) would do)
         if ctx.n_slots:
-            return (None, gt0, gtk, gperiph, geps, gtheta, None, gdict, None, None, None, None, None,
-                    *_slot_grads(ctx, gx))
-        return (gx if ctx.needs_input_grad[0] else None, gt0, gtk, gperiph, geps, gtheta, None, gdict,
-                None, None, None, None, None)
+            return _input_grads(table0=tables[0], tablek=tables[1], periph=gperiph, eps=geps, theta=gtheta, ptab=gdict,
+                                slots=_slot_grads(ctx, gx))
+        return _input_grads(x=gx if _needs(ctx, "x") else None, table0=tables[0], tablek=tables[1], periph=gperiph, eps=geps,
+                            theta=gtheta, ptab=gdict)
 
 
-def _finish_gtheta(ctx, gtheta, theta, galphas_done, k_act):
-    """d/dalphas through theta (geo_theta.hip) when the finishing launch has not already produced it."""
-    if gtheta is not None and ctx.alphas is not None and not galphas_done:
+# The one place that knows where KHopAggregate.forward's inputs stand: the names of its arguments after ctx, in order (the
+# per-hop slots `*xs` follow them).
+_INPUTS = ("x", "table0", "tablek", "periph", "eps", "theta", "xbias", "ptab", "csr", "k_act", "mode", "uid", "cells")
+_INPUT_POS = {n: i for i, n in enumerate(_INPUTS)}
+
+
+def _needs(ctx, name):
+    return ctx.needs_input_grad[_INPUT_POS[name]]
+
+
+def _input_grads(slots=(), **named):
+    """The tuple backward hands autograd: the named gradients at their inputs' positions, None elsewhere, then the slots'."""
+    assert named.keys() <= _INPUT_POS.keys()
+    return (*(named.get(n) for n in _INPUTS), *slots)
+
+
+# This layer's share of the peripheral dictionary's gradient, and where it is:
+#   grad           the tensor, or None (nothing asked, or the share waits elsewhere: `parked`);
+#   includes_cell  a finishing launch has already ADDED the dictionary cell's buffer (the later layers' shares) into `grad`;
+#   parked         the share waits in the cell's list (_SlotGradCell.park_dict) for the ONE kpgnn_dict_grad_multi launch of
+#                  the pass: `grad` is None.
+_DictShare = collections.namedtuple("_DictShare", "grad includes_cell parked", defaults=(None, False, False))
+
+
+# ---- stage 1: the epilogue's backward - g = dL/dS from dL/dout
+def _epilogue_bwd(ctx, pre, theta, periph, ptab, gout, want_tables, want_gdict, want_gperiph):
+    """Returns (g, gperiph, gtheta, galphas, tables, share).  galphas: d/dalphas where the finishing launch produced it (gtheta
+    is then None).  tables = (gtable0, gtablek) and share (a _DictShare) only from the fused route, else None: the table stage
+    then follows."""
+    if (theta is not None and ctx.mode == MODE_GINPLUS and want_tables and periph is None and not want_gperiph
+            and _combine_table_grad_ok(ctx.csr, pre, ctx.n_code0 + (ctx.n_codek if ctx.k_act > 1 else 0), ctx.n_dict)):
+        r = _epilogue_fused(ctx, pre, theta, ptab, gout, want_gdict)
+        if r is not None:
+            return r
+    if theta is not None or ctx.mode in (MODE_GINPLUS, MODE_GCN):
+        return _epilogue_combine_bwd(ctx, pre, theta, periph, ptab, gout, want_gperiph)
+    return gout, (gout if want_gperiph else None), None, None, None, None            # identity: g = dL/dout = dL/dP
+
+
+def _epilogue_fused(ctx, pre, theta, ptab, gout, want_gdict):
+    """KP-GIN+ with the fused combine, dictionary P and edge-code tables: ONE kernel computes dL/dS from S and gh, writes it
+    for the gather and takes the table gradients from the LDS copy of each tile.  The dictionary gradient comes from gh alone:
+    large batches park it for the pass's one multi-layer launch or run kpgnn_dict_grad, whose partial sums the same finishing
+    launch adds up; small ones let the dictionary rows ride along the walk.  None: no fused kernel for this shape after all."""
+    csr, uid, cell = ctx.csr, ctx.uid, ctx.dict_cell
+    acc = cell.buf if (want_gdict and cell is not None) else None     # later layers' share: the finishing launch adds to it
+    dg, parked = None, False
+    if want_gdict and pre.shape[0] >= 4096:
+        if cell is not None and dict_multi_ok(uid, ctx.n_dict, theta, gout):
+            cell.park_dict(uid, theta, gout)        # ONE launch for all the layers, run by the last of them
+            parked, acc = True, None
+        else:
+            dg = dict_grad_raw(uid, ctx.n_dict, theta, gout, defer=True)
+    in_walk = ctx.n_dict if (want_gdict and dg is None and not parked) else 0    # small batches: the dictionary rows ride along
+    r = combine_table_grad_raw(csr, pre, gout, theta, ptab, uid, ctx.n_code0, ctx.n_codek, want_gtheta=_needs(ctx, "theta"),
+                               alphas=ctx.alphas, extra=dg, dict_rows=in_walk, gdict_acc=acc)
+    if r is None and in_walk:                       # the one retry: without dictionary rows (and without the cell's buffer)
+        r = combine_table_grad_raw(csr, pre, gout, theta, ptab, uid, ctx.n_code0, ctx.n_codek, want_gtheta=_needs(ctx, "theta"),
+                                   alphas=ctx.alphas)
+        in_walk = 0
+    if r is None:
+        if parked:                                  # (the share goes the plain way, through the table stage)
+            cell.unpark_dict()
+        if dg is not None:
+            raise _lib.KpgnnError("table_grad refused a shape after dict_grad deferred its reduction to it")
+        return None
+    g, gtheta, gt0, gtk = r[:4]
+    gtheta, galphas = (None, gtheta[1]) if isinstance(gtheta, tuple) else (gtheta, None)
+    if dg is not None:
+        share = _DictShare(dg[0] if acc is None else acc, includes_cell=acc is not None)
+    elif in_walk:
+        share = _DictShare(r[4], includes_cell=acc is not None)
+    elif want_gdict and not parked:
+        share = _DictShare(table_grad_raw(csr, g, 0, 0, edges=False, uid=uid, n_dict=ctx.n_dict, theta=theta, gh=gout)[2])
+    else:
+        share = _DictShare(parked=parked)
+    return g, None, gtheta, galphas, (gt0, gtk), share
+
+
+def _epilogue_combine_bwd(ctx, pre, theta, periph, ptab, gout, want_gperiph):
+    """kpgnn_combine_bwd: the activation's and / or the fused combine's backward (g, dL/dP as gv, theta gradient)."""
+    fused = theta is not None
+    g, gv, gtheta = combine_bwd_raw(ctx.mode, pre, gout, theta, periph, ptab, ctx.uid,
+                                    want_gtheta=fused and _needs(ctx, "theta"),
+                                    want_gv=fused and want_gperiph, alphas=ctx.alphas if fused else None)
+    # (geometric combine: d/dalphas came with the same finishing launch)
+    gtheta, galphas = (None, gtheta[1]) if isinstance(gtheta, tuple) else (gtheta, None)
+    return g, (gv if fused else (gout if want_gperiph else None)), gtheta, galphas, None, None
+
+
+# ---- stage 2: table gradients (edge codes + peripheral dictionary), column-private kernel; not after the fused epilogue
+def _table_stage(ctx, g, gout, theta, want_tables, want_gdict):
+    """Returns ((gtable0, gtablek), tables_in_gather, share): tables_in_gather = the gather computes the table gradients
+    (GCN's per-edge weights, or a shape kpgnn_table_grad refuses) and the pair is still (None, None)."""
+    gt0 = gtk = gdict = None
+    if not (want_tables or want_gdict):
+        return (gt0, gtk), False, _DictShare()
+    csr, uid, cell = ctx.csr, ctx.uid, ctx.dict_cell
+    fused = theta is not None
+    need_act = ctx.mode in (MODE_GINPLUS, MODE_GCN)
+    edges_here = want_tables and ctx.mode != MODE_GCN   # GCN weights its table grads per edge: fused atomics
+    dict_here = want_gdict and (fused or not need_act)  # g == dL/dP only without an activation
+    res = extra = acc = None
+    # (below ~4K nodes the walk's own dictionary path is cheaper than a second kernel: 1.44 vs 1.52 ms per step at
+    #  batch 64, where every launch is latency-bound)
+    if dict_here and fused and (g.shape[0] >= 4096 or not edges_here):   # from gh alone (20 MB, not [N,K,D])
+        # (its partial sums are added up by table_grad's finishing launch when one follows)
+        dg = dict_grad_raw(uid, ctx.n_dict, theta, gout, defer=edges_here)
+        if dg is not None:
+            dict_here = False
+            if edges_here:
+                gdict, extra = dg[0], dg
+            else:
+                gdict = dg
+    if edges_here or dict_here:
+        if dict_here and cell is not None:
+            acc = cell.buf                       # later layers' share: this call's finishing launch adds to it
+        res = table_grad_raw(csr, g, ctx.n_code0, ctx.n_codek, edges=edges_here,
+                             uid=uid if dict_here else None, n_dict=ctx.n_dict if dict_here else 0,
+                             theta=theta if fused else None, gh=gout if fused else None, extra=extra, gdict_acc=acc)
+        if res is None and extra is not None:
+            raise _lib.KpgnnError("table_grad refused a shape after dict_grad deferred its reduction to it")
+    if res is not None:
+        gt0, gtk = res[0], res[1]
+        gdict = res[2] if gdict is None else gdict
+    if want_gdict and gdict is None:  # activation without fused combine (or oversize tables): dL/dP = gout
+        r2 = table_grad_raw(csr, gout if not fused else (gout.unsqueeze(1) * theta.unsqueeze(0)),
+                            0, 0, edges=False, uid=uid, n_dict=ctx.n_dict)
+        if r2 is None:
+            raise _lib.KpgnnError("peripheral dictionary too large for the LDS table-gradient kernel; "
+                                  "pass a dense peripheral_attr instead")
+        gdict = r2[2]
+    return (gt0, gtk), want_tables and (res is None or not edges_here), _DictShare(gdict, res is not None and acc is not None)
+
+
+# ---- stage 3: this layer's dictionary share against the cell of a dictionary that several layers read
+def _settle_dict_share(cell, first, share, n_dict):
+    """What this layer hands autograd for the dictionary: its own share without a cell; with one, None unless it is the
+    FIRST reader in forward order - the last to run backward - which hands over the total and clears the cell.
+
+      parked and not first         nothing: the share waits in the cell's list, a share in `cell.buf` stays where it is.
+      otherwise                    total = share.grad
+        first                        + the ONE multi-layer launch over what the layers parked (its own share included),
+        not share.includes_cell      + cell.buf, if there is one                                    - in THIS order;
+      first                        return the total, clear the cell;  else  cell.buf = total, return None.
+
+    `cell.buf` is added here exactly when no finishing launch has added it already (the single-scope backward wrote this as
+    "the buffer was not handed to a launch, and (not done or dict_parked)", done = the fused epilogue ran):
+      fused epilogue, dict_grad deferred or rows in the walk   the launch was given cell.buf: includes_cell whenever there
+                                                               was one, and nothing to add when there was none;
+      fused epilogue, after the retry without dictionary rows  the share is a fresh tensor: added here;
+      fused epilogue, parked (this is then the first reader)   the total starts from the multi launch's result: added here;
+      table stage                                              includes_cell only if table_grad took the dictionary rows
+                                                               itself and was given cell.buf; every other path (dict_grad,
+                                                               the dL/dP = gout fallback): added here."""
+    if cell is None:
+        return share.grad
+    if share.parked and not first:
+        return None
+    total = share.grad
+    if first:
+        items = cell.take_dicts()
+        if items:
+            gm = dict_grad_multi_raw(items, n_dict)
+            total = gm if total is None else total + gm
+    if not share.includes_cell and cell.buf is not None:
+        total = total + cell.buf                     # (a path without the accumulating launch: add the parked share the plain way)
+    cell.buf = None if first else total
+    return total if first else None
+
+
+# ---- stage 4: the transposed gather - dL/dx (or the hop slots' gradients) from g
+def _pull_form_applies(ctx, g, eps, tables_in_gather):
+    """Pull form (KP-GIN+ history pattern, large batches): this layer's hop slabs of g are parked with the states it read as
+    slots >= 1; the state it read as slot 0 - whose last reader it is - gets its WHOLE gradient from one gather."""
+    return (PULL_GATHER and ctx.n_slots > 0 and ctx.cells is not None and ctx.mode == MODE_GINPLUS and not tables_in_gather
+            and eps is None and g.dtype == torch.float32 and g.shape[0] >= 4096 and g.shape[2] % 4 == 0 and ctx.k_act <= 16
+            and all(g[:, k].is_contiguous() for k in range(ctx.k_act)))
+
+
+def _gather_pull(ctx, g):
+    """d/d(slot-0 state): one gather over the slabs later layers parked for it, this layer's hop-0 slab and whatever share
+    the cell already holds.  Parks this layer's other slabs with the states it read them from."""
+    for k in range(1, ctx.k_act):
+        ctx.cells[k].park_slab(k, g[:, k])
+    c0 = ctx.cells[0]
+    pend = c0.take_slabs()
+    top = max(pend) if pend else 0
+    zeros = None
+    slabs = [g[:, 0]]
+    for h in range(1, top + 1):
+        t = pend.get(h)
+        if t is None:            # (a hop nobody parked - a pruned backward pass: gathered from zeros)
+            zeros = torch.zeros_like(slabs[0]) if zeros is None else zeros
+            t = zeros
+        slabs.append(t)
+    hb = c0.buf
+    shape = tuple(slabs[0].shape)
+    ok = lambda t: t is not None and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == shape
+    hinit = hb if ok(hb) else None
+    ext = c0.take_addend()
+    hinit2 = ext if ok(ext) else None
+    total = khop_pull_gather(ctx.csr, slabs[:16], hinit, hinit2)
+    if hb is not None and hinit is None:
+        total = total + hb.view_as(total)          # (odd layout: add the parked share the plain way)
+    if ext is not None and hinit2 is None:
+        total = total + ext.view_as(total)
+    c0.buf = None
+    return total
+
+
+def _x_cell_accumulator(ctx, g, tables_in_gather):
+    """The buffer of the state's cell (x_state) when kpgnn_aggregate_bwd can add dL/dx into it in place, else None."""
+    if (ctx.x_cell is not None and ctx.x_cell.buf is not None and _needs(ctx, "x") and ctx.k_act <= 32
+            and ctx.mode != MODE_GCN and not tables_in_gather):
+        b = ctx.x_cell.buf
+        if b.is_contiguous() and b.numel() == g.numel() and b.dtype == torch.float32:
+            return b
+    return None
+
+
+def _gather_push(ctx, g, eps, tables_in_gather):
+    """kpgnn_aggregate_bwd, adding into the cells' buffers where it can, and whatever was left for this layer's states by
+    readers that counted on another form.  Returns (gx, (gtable0, gtablek) of the gather)."""
+    xbuf = _x_cell_accumulator(ctx, g, tables_in_gather)
+    gx, a0, ak = aggregate_bwd_raw(ctx.csr, ctx.k_act, ctx.mode, g, eps, ctx.n_code0, ctx.n_codek, tables_in_gather,
+                                   slots=ctx.n_slots > 0, slot_bufs=_slot_bufs(ctx), gx_accum=xbuf)
+    if ctx.n_slots > 0 and ctx.cells is not None:
+        ext = ctx.cells[0].take_addend()      # (a share handed over for the pull form that this layer could not run)
+        if ext is not None:
+            gx = list(gx)
+            gx[0] = gx[0] + ext.view_as(gx[0])
+        pend = ctx.cells[0].take_slabs()      # (later layers ran the pull form, this one could not: their slabs for ITS slot-0 state)
+        if pend:
+            zeros = torch.zeros_like(next(iter(pend.values())))
+            extra = khop_pull_gather(ctx.csr, [pend.get(h, zeros) for h in range(0, max(pend) + 1)], None)
+            gx = list(gx)
+            gx[0] = gx[0] + extra
+    if ctx.x_cell is not None:
+        if xbuf is None and ctx.x_cell.buf is not None and _needs(ctx, "x"):
+            gx = gx + ctx.x_cell.buf.view_as(gx)     # (odd layout: add the parked share the plain way)
+        ctx.x_cell.buf = None
+    return gx, (a0, ak)
+
+
+# ---- stage 5: the scalar tails
+def _eps_grad(ctx, g, eps, x_saved, xbias):
+    if eps is None or not _needs(ctx, "eps") or ctx.mode != MODE_GIN:
+        return None
+    refuse_dynamic_rows("the eps gradient (framework sum over rows)", g.shape[0])
+    xe = x_saved
+    if xbias is not None and xe.shape[1] > 1:
+        xe = torch.cat([xe[:, :1], xe[:, 1:] + xbias], dim=1)
+    return (g * xe).sum().reshape(eps.shape)
+
+
+def _finish_gtheta(ctx, gtheta, galphas, theta):
+    """What the `theta` input gets: d/dalphas - through theta (geo_theta.hip) when the finishing launch has not already
+    produced it - where the input was a GeometricCombine's alphas, else the theta gradient."""
+    if galphas is not None:
+        return galphas
+    if gtheta is not None and ctx.alphas is not None:
         galpha = torch.empty_like(ctx.alphas)
         _lib.launch("kpgnn_geo_theta_bwd", galpha.device,
-                    ctx.alphas.data_ptr(), theta.data_ptr(), gtheta.data_ptr(), k_act, ctx.alphas.numel(), galpha.data_ptr())
+                    ctx.alphas.data_ptr(), theta.data_ptr(), gtheta.data_ptr(), ctx.k_act, ctx.alphas.numel(), galpha.data_ptr())
         return galpha
     return gtheta
 
@@ -969,69 +1058,89 @@ def _backward_pass_id():
         return -1
 
 
+class _PassTagged:
+    """A value and the backward pass that wrote it (torch._C._current_graph_task_id()): read from any other pass, it is gone."""
+    __slots__ = ("v", "task")
+
+    def __init__(self):
+        self.v, self.task = None, -1
+
+    def get(self):
+        if self.v is not None and self.task != _backward_pass_id():
+            self.v = None                # written by another backward pass: stale
+        return self.v
+
+    def set(self, v):
+        self.v = v
+        self.task = _backward_pass_id() if v is not None else -1
+
+    def take(self):
+        v = self.get()
+        self.v, self.task = None, -1
+        return v
+
+
 class _SlotGradCell:
     """Gradient buffer of one state tensor that several layers read as a hop slot (see khop_aggregate).
 
     Cells carry part of d/dstate OUTSIDE autograd: a reader parks its share in `buf`, later readers (in backward order) add
     to it in place and the state's last reader hands autograd the total and clears the cell.  That is only sound within ONE
     backward pass.  A pruned or partial pass (`autograd.grad(score, some_params, retain_graph=True)`) may park a share that
-    no reader of ITS pass ever collects; the parked buffer is therefore tagged with the pass that wrote it
-    (torch._C._current_graph_task_id()) and reads from any other pass see an empty cell - a stale share is never added to
-    a later pass's gradient (tests/test_gpu_parity.py::test_gradient_cells_survive_a_partial_backward)."""
-    __slots__ = ("_buf", "_task", "_pend", "_ptask", "_add", "_atask", "pull_reader", "_dg", "_dgtask")
+    no reader of ITS pass ever collects; everything parked is therefore tagged with the pass that wrote it (_PassTagged) and
+    reads from any other pass see an empty cell - a stale share is never added to a later pass's gradient
+    (tests/test_gpu_parity.py::test_gradient_cells_survive_a_partial_backward)."""
+    __slots__ = ("_share", "_slabs", "_addend", "_dicts", "pull_reader")
 
     def __init__(self):
-        self._buf, self._task = None, -1
-        self._pend, self._ptask = None, -1
-        self._add, self._atask = None, -1       # one more [N,D] addend of the pull gather (the residual branch's share)
+        self._share = _PassTagged()             # `buf`
+        self._slabs = _PassTagged()             # {hop: [N,D] slab} of the pull gather
+        self._addend = _PassTagged()            # one more [N,D] addend of the pull gather (the residual branch's share)
+        self._dicts = _PassTagged()             # dictionary cell: the (uid, theta, gh) of the layers whose share waits for ONE launch
         self.pull_reader = False                # set in forward by the state's slot-0 reader when its backward will be the pull
                                                 # form (fused geometric combine): only then is an addend worth parking
-        self._dg, self._dgtask = None, -1       # dictionary cell: the (uid, theta, gh) of the layers whose share waits for ONE launch
+
+    # what is held whatever pass wrote it (the tests look at a cell after the backward pass has ended)
+    _buf = property(lambda self: self._share.v)
+    _add = property(lambda self: self._addend.v)
 
     # One dictionary-gradient launch for all the layers that read the dictionary (dict_grad_multi_raw): every reader parks
-    # (uid view, theta, gh); the first reader in forward order - the last to run backward - runs the launch.  Pass-tagged like `buf`.
+    # (uid view, theta, gh); the first reader in forward order - the last to run backward - runs the launch.
     def park_dict(self, uid, theta, gh):
-        if self._dg is None or self._dgtask != _backward_pass_id():
-            self._dg, self._dgtask = [], _backward_pass_id()
-        self._dg.append((uid, theta, gh))
+        if self._dicts.get() is None:
+            self._dicts.set([])
+        self._dicts.v.append((uid, theta, gh))
+
+    def unpark_dict(self):
+        """Takes back the share this pass parked last (its layer hands it over another way after all)."""
+        self._dicts.get().pop()
 
     def take_dicts(self):
-        t = self._dg if self._dgtask == _backward_pass_id() else None
-        self._dg, self._dgtask = None, -1
-        return t or []
+        return self._dicts.take() or []
 
     def park_addend(self, t):
-        self._add, self._atask = t, _backward_pass_id()
+        self._addend.set(t)
 
     def take_addend(self):
-        t = self._add if self._atask == _backward_pass_id() else None
-        self._add, self._atask = None, -1
-        return t
-
+        return self._addend.take()
 
     # Pull form of the backward gather (khop_pull_gather): a later reader of the state does not add its share into `buf` -
     # it leaves the hop slab of ITS dL/dS here, keyed by the hop slot it read the state at, and the state's last reader
-    # gathers from all of them in one launch.  Same pass tagging as `buf`.
+    # gathers from all of them in one launch.
     def park_slab(self, hop, slab):
-        if self._pend is None or self._ptask != _backward_pass_id():
-            self._pend, self._ptask = {}, _backward_pass_id()
-        self._pend[hop] = slab
+        if self._slabs.get() is None:
+            self._slabs.set({})
+        self._slabs.v[hop] = slab
 
     def take_slabs(self):
-        p = self._pend if (self._pend is not None and self._ptask == _backward_pass_id()) else {}
-        self._pend, self._ptask = None, -1
-        return p
+        return self._slabs.take() or {}
 
     @property
     def buf(self):
-        if self._buf is not None and self._task != _backward_pass_id():
-            self._buf = None                # parked by another backward pass: stale
-        return self._buf
+        return self._share.get()
 
     @buf.setter
     def buf(self, v):
-        self._buf = v
-        self._task = _backward_pass_id() if v is not None else -1
+        self._share.set(v)
 
 
 def state_cell(t):
@@ -1080,12 +1189,7 @@ def khop_aggregate(x, csr, k_act, mode, table0=None, tablek=None, periph=None, e
     if isinstance(x, (list, tuple)):
         cells = None
         if share_slot_grads and torch.is_grad_enabled():
-            cells = []
-            for t in x:
-                c = getattr(t, "_kp_slot_cell", None)
-                if c is None:
-                    c = t._kp_slot_cell = _SlotGradCell()
-                cells.append(c)
+            cells = [state_cell(t) for t in x]
         return KHopAggregate.apply(None, table0, tablek, periph, eps, theta, xbias, ptab, csr, k_act, mode, uid, cells, *x)
     # x_state: the [N, K*D] state tensor that x is a view of, when the caller guarantees that this call is the LAST of the
     # state's readers to run backward (the bodies: the jumping-knowledge projection and the next norm's residual branch read
