@@ -848,6 +848,37 @@ int kpgnn_segment_pool_fwd(const kpgnn_pool_desc* d, kpgnn_stream_t stream);
 int kpgnn_segment_pool_bwd(const kpgnn_pool_desc* d, kpgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Max graph readout (csrc/pool_max.hip; models/GraphClassification.py:24-34 "max": PyG 2.1.0 global_max_pool, which is
+ * torch_scatter.scatter_max).  With live = *n_dyn when given, else N:
+ *   out[g,c] = max of x[n,c] over graph_ptr[g] <= n < min(graph_ptr[g+1], live)
+ *   arg[g,c] = the LOWEST such row n that attains the max: the tie rule of torch_scatter's CPU kernel and of kpgnn_jk_reduce_*'s max,
+ *              which gives a tie to the lowest slot.  One winner per (graph, column).
+ * NaN: a NaN in a live row makes the column's result NaN (as amax does) and arg the FIRST NaN row; once a NaN is taken,
+ * nothing replaces it.  An empty graph gives out = -inf, arg = -1, and no gradient flows.  Rows at or beyond graph_ptr[G]
+ * and rows at or beyond the live count are never read.
+ * Backward, for every live row n with g = batch[n]:  gx[n,c] = (arg[g,c] == n) ? gout[g,c] : +0.0f.  Each live row is
+ * written exactly once, dead rows are not written; there is no zero-fill launch and there are no atomics, so both
+ * directions are bitwise reproducible.  One launch per direction.
+ * D <= 1024 and ceil(D / vec) <= 256 lanes (KPGNN_ELIMIT beyond), vec as for kpgnn_segment_pool_*.  G == 0 (forward) and
+ * N == 0 (backward) return KPGNN_OK without a launch.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct kpgnn_pool_max_desc {
+    int64_t N;                  /* nodes */
+    int32_t G, D;               /* graphs, feature width */
+    const int32_t* graph_ptr;   /* device [G+1], non-decreasing (forward) */
+    const int64_t* batch;       /* device [N]: graph of node n (backward only) */
+    const float* x; int64_t x_stride;      /* device [N,D] (forward) */
+    float* out;                 /* device [G,D] contiguous (forward) */
+    int32_t* arg;               /* device [G,D] contiguous winners: row index, -1 for an empty graph; NULL in forward: not kept */
+    const float* gout;          /* device [G,D] contiguous (backward) */
+    float* gx; int64_t gx_stride;          /* device [N,D] (backward, live rows overwritten) */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= N; kpgnn_wgrad_desc explains); NULL: all N rows */
+} kpgnn_pool_max_desc;
+
+int kpgnn_segment_max_fwd(const kpgnn_pool_max_desc* d, kpgnn_stream_t stream);
+int kpgnn_segment_max_bwd(const kpgnn_pool_max_desc* d, kpgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Virtual node (csrc/virtual_node.hip; models/GNNs.py:196-199,227-230: h + vn[batch], global_add_pool(h) + vn):
  *   out[n,:]    = x[n,:] + v[g,:]               for the nodes n of graph g (graph_ptr[g] .. graph_ptr[g+1])
  *   pooled[g,:] = sum_n out[n,:] + v[g,:]       (optional; an empty graph gives v[g,:])

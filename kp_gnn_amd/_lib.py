@@ -304,6 +304,15 @@ class PoolDesc(ctypes.Structure):
     ]
 
 
+class PoolMaxDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("G", c_i32), ("D", c_i32),
+        ("graph_ptr", c_vp), ("batch", c_vp), ("x", c_vp), ("x_stride", c_i64), ("out", c_vp), ("arg", c_vp),
+        ("gout", c_vp), ("gx", c_vp), ("gx_stride", c_i64),
+        ("n_dyn", c_vp),
+    ]
+
+
 class VnDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i64), ("G", c_i32), ("D", c_i32),
@@ -475,6 +484,8 @@ SIGNATURES = {
     "kpgnn_enc_tables_bwd": (ctypes.c_int, [ctypes.POINTER(EncTablesDesc), c_vp]),
     "kpgnn_segment_pool_fwd": (ctypes.c_int, [ctypes.POINTER(PoolDesc), c_vp]),
     "kpgnn_segment_pool_bwd": (ctypes.c_int, [ctypes.POINTER(PoolDesc), c_vp]),
+    "kpgnn_segment_max_fwd": (ctypes.c_int, [ctypes.POINTER(PoolMaxDesc), c_vp]),
+    "kpgnn_segment_max_bwd": (ctypes.c_int, [ctypes.POINTER(PoolMaxDesc), c_vp]),
     "kpgnn_vn_add_pool": (ctypes.c_int, [ctypes.POINTER(VnDesc), c_vp]),
     "kpgnn_dropout_fwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
     "kpgnn_dropout_bwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),

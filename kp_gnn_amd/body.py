@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from .layers.gine import GINEConv
 from .ops import (DictPeripheral, attention_pool, body_norm, dropout_add, embedding_rows, enc_tables, jk_lstm_applies, jk_lstm_score,
                   jk_native_applies, jk_reduce,
-                  native_dropout_applies, refuse_dynamic_rows, segment_pool, table_gather_sum, virtual_node_add)
+                  native_dropout_applies, refuse_dynamic_rows, segment_max, segment_pool, table_gather_sum, virtual_node_add)
 from .ops_dense import (JKConcatLinear, batch_norm_act, head_linear, jk_concat_linear_nograd, mlp_linear_bn_relu_x2,
                         prepare_mlp_splits, score_head)
 
@@ -707,7 +707,15 @@ def global_mean_pool(x, batch, size=None):
 
 
 def global_max_pool(x, batch, size=None):
+    """PyG 2.1.0's global_max_pool.  2-D fp32 device tensors run ops.segment_max: one winner per (graph, column), the lowest
+    row of a tie, takes the whole gradient, as torch_scatter.scatter_max gives it.  Everything else keeps the framework's
+    scatter, whose backward splits a tied column's gradient evenly - and which cannot tell the dead rows of a
+    capacity-shaped batch from live ones, so on the device it refuses them."""
     size = _num_graphs(batch, size)
+    if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32:
+        return segment_max(x, batch, size)
+    if x.is_cuda:
+        refuse_dynamic_rows("max readout on the framework path", x.shape[0])
     idx = batch.view(-1, 1).expand_as(x)
     return x.new_full((size, x.size(1)), float("-inf")).scatter_reduce(0, idx, x, reduce="amax")
 

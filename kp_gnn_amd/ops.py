@@ -1428,6 +1428,63 @@ def segment_pool(x, batch, num_graphs, mean=False):
     return SegmentPool.apply(x, batch.long() if batch.dtype != torch.int64 else batch, graph_ptr_of(batch, num_graphs), num_graphs, mean)
 
 
+def _segment_max_launch(x, ptr, num_graphs, keep_arg):
+    """([G,D] column-wise max of the rows of x [N,D] per graph, int32 [G,D] winning rows or None): one kpgnn_segment_max_fwd
+    launch.  A strided x with unit column stride is read in place."""
+    N, D = x.shape
+    if x.stride(1) != 1 or x.stride(0) < D:
+        x = x.contiguous()
+    out = torch.empty((num_graphs, D), dtype=torch.float32, device=x.device)
+    arg = torch.empty((num_graphs, D), dtype=torch.int32, device=x.device) if keep_arg else None
+    d = _lib.PoolMaxDesc()
+    d.N, d.G, d.D = N, num_graphs, D
+    d.n_dyn = dyn_ptr(N)
+    d.graph_ptr, d.x, d.x_stride, d.out, d.arg = ptr.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(), _ptr(arg)
+    _lib.launch("kpgnn_segment_max_fwd", x.device, ctypes.byref(d))
+    return out, arg
+
+
+class SegmentMax(torch.autograd.Function):
+    """out[g] = column-wise max of the rows of graph g (kpgnn_segment_max_*): the lowest row that attains a column's max is its
+    one winner and takes the whole gradient (torch_scatter.scatter_max, not amax's even split).  One launch per direction;
+    only `batch` and the int32 winners are kept for backward, neither x nor the result."""
+
+    @staticmethod
+    def forward(ctx, x, batch, ptr, num_graphs):
+        out, arg = _segment_max_launch(x, ptr, num_graphs, True)
+        ctx.save_for_backward(batch, arg)
+        ctx.dims = (x.shape[0], x.shape[1], num_graphs)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        batch, arg = ctx.saved_tensors
+        N, D, G = ctx.dims
+        gout = gout.contiguous()
+        gx = torch.empty((N, D), dtype=torch.float32, device=gout.device)
+        d = _lib.PoolMaxDesc()
+        d.N, d.G, d.D = N, G, D
+        d.n_dyn = dyn_ptr(N)
+        d.batch, d.arg, d.gout, d.gx, d.gx_stride = batch.data_ptr(), arg.data_ptr(), gout.data_ptr(), gx.data_ptr(), D
+        _lib.launch("kpgnn_segment_max_bwd", gout.device, ctypes.byref(d))
+        return gx, None, None, None
+
+
+def segment_max(x, batch, num_graphs):
+    """Max readout of [N,D] node rows per graph on the HIP kernels (fp32 device tensors, int64 sorted batch); an empty graph
+    gives -inf.  Without autograd (grad disabled, or x does not require it) no winners are kept and nothing but the result is
+    allocated."""
+    _require_cuda(x, batch)
+    if x.shape[1] > 256:       # (the row shapes instantiated stop at 256 floats, as for segment_pool: wider rows take the framework's scatter)
+        refuse_dynamic_rows("max readout of rows wider than 256", x.shape[0])
+        idx = batch.long().view(-1, 1).expand_as(x)
+        return x.new_full((num_graphs, x.shape[1]), float("-inf")).scatter_reduce(0, idx, x, reduce="amax")
+    ptr = graph_ptr_of(batch, num_graphs)
+    if not (torch.is_grad_enabled() and x.requires_grad):
+        return _segment_max_launch(x, ptr, num_graphs, False)[0]
+    return SegmentMax.apply(x, batch.long() if batch.dtype != torch.int64 else batch, ptr, num_graphs)
+
+
 # ------------------------------------------------------------------------------------------------ virtual node
 def _vn_launch(x, v, ptr, num_graphs, want_pool, out=None):
     """(x + v[g], sum of that per graph + v or None) as one kpgnn_vn_add_pool launch; x [N,D], v [G,D] (row stride 0 allowed);

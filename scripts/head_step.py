@@ -1,10 +1,11 @@
-"""Training-step time (forward + loss + backward, no optimiser) of two task-head workloads, with the native head and with the
+"""Training-step time (forward + loss + backward, no optimiser) of three task-head workloads, with the native head and with the
 same head written in plain torch ops (--framework-head), on synthetic_zinc_batch data:
 
     graph_property   KP-GIN+, K = 6, L = 6, h = 96, 128 graphs, attention readout, MSE      (train_graph_property.py's default)
     tu               KP-GIN,  K = 2, L = 2, h = 32, 128 graphs, sum readout, C = 2, NLL     (train_TU.py / train_EXP.py)
+    tu_max           the same with the max readout (--pooling_method max)
 
-    python scripts/head_step.py                       # both workloads, both heads, 3 interleaved runs per side, one JSON line
+    python scripts/head_step.py                       # every workload, both heads, 3 interleaved runs per side, one JSON line
     python scripts/head_step.py --framework-head      # the framework head only
     python scripts/head_step.py --native-head         # the native head only
 
@@ -26,6 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 WORKLOADS = {
     "graph_property": dict(model="KPGINPlus", K=6, L=6, H=96, graphs=128, pooling="attention", task="mse"),
     "tu": dict(model="KPGIN", K=2, L=2, H=32, graphs=128, pooling="sum", task="nll", C=2),
+    "tu_max": dict(model="KPGIN", K=2, L=2, H=32, graphs=128, pooling="max", task="nll", C=2),
 }
 
 
@@ -65,6 +67,8 @@ def framework_head(model, w, x, b, y):
         e = (gate - mx[idx]).exp()
         alpha = e / (gate.new_zeros(G).index_add_(0, idx, e)[idx] + 1e-16)
         pooled = x.new_zeros((G, x.shape[1])).index_add_(0, idx, alpha.unsqueeze(-1) * x)
+    elif w["pooling"] == "max":
+        pooled = x.new_full((G, x.shape[1]), float("-inf")).scatter_reduce(0, idx.view(-1, 1).expand_as(x), x, reduce="amax")
     else:
         pooled = x.new_zeros((G, x.shape[1])).index_add_(0, idx, x)
     if w["task"] == "mse":
