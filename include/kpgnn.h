@@ -1354,6 +1354,73 @@ size_t kpgnn_body_norm_workspace_bytes(int64_t N, int32_t C);
 int kpgnn_body_norm_fwd(const kpgnn_norm_desc* d, kpgnn_stream_t stream);
 int kpgnn_body_norm_bwd(const kpgnn_norm_desc* d, kpgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Resistance-distance node feature (csrc/resistance.hip; data_utils.py:280-303, `--use_rd`).  For each graph g of
+ * n = node_ptr[g+1] - node_ptr[g] nodes, with A the summed adjacency of its edges (ones; duplicates add, the diagonal is
+ * ignored as scipy's csgraph.laplacian ignores it) and L+ the pseudo-inverse of the Laplacian D - A:
+ *   out[node_ptr[g] + y] = (float)(((L+[0,0] + L+[y,y]) - L+[0,y]) - L+[y,0])            in double, in that order: out[.. + 0] == 0.0f
+ * L+ is not computed by an SVD: with the connected components c of sizes m_c, M = D - A + sum_c (1/m_c) 1_c 1_c^T is
+ * symmetric positive definite, M^-1 comes from an in-place Gauss-Jordan sweep without pivoting (double, in LDS), and
+ * L+ = M^-1 - sum_c (1/m_c) 1_c 1_c^T.  A node in another component than node 0 gets L+[0,0] + L+[y,y], as pinv gives.
+ * status[g] (written for every graph of `graph_ids`; out is written only where it is 0):
+ *   KPGNN_RD_OK 0          served
+ *   KPGNN_RD_ASYMMETRIC 1  A != A^T: a directed list, the host route's job
+ *   KPGNN_RD_TOO_LARGE 2   n > max_nodes of this launch (the cap of any launch is 128: one 128 x 129 double matrix in LDS)
+ *   KPGNN_RD_PIVOT 3       a pivot <= 0 or not finite
+ *   KPGNN_RD_RANGE 4       an edge endpoint outside [node_ptr[g], node_ptr[g+1])
+ * One launch serves the graphs `graph_ids[0 .. n_ids)`.  max_nodes <= 32: one wavefront per graph, four graphs per block, no
+ * block barrier; above: one block per graph with dynamic LDS for max_nodes.  The caller buckets its graphs by size and makes
+ * one call per class.  The count matrix is built with LDS integer atomics, so the result does not depend on the edge order;
+ * no atomics to global memory, one workgroup per graph in a fixed order: bitwise reproducible.  n_ids == 0 returns KPGNN_OK
+ * without a launch, n == 0 writes status 0 alone.  Ids outside [0, G) in graph_ids are skipped; edges are read from
+ * [edge_ptr[g], edge_ptr[g+1]) clipped to [0, E).
+ * ---------------------------------------------------------------------------------------------- */
+enum { KPGNN_RD_OK = 0, KPGNN_RD_ASYMMETRIC = 1, KPGNN_RD_TOO_LARGE = 2, KPGNN_RD_PIVOT = 3, KPGNN_RD_RANGE = 4 };
+#define KPGNN_RD_MAX_NODES 128
+#define KPGNN_RD_WAVE_NODES 32
+
+typedef struct kpgnn_rd_desc {
+    int32_t G, n_ids;           /* graphs of the call; graphs this launch serves */
+    const int64_t* node_ptr;    /* device [G+1] */
+    const int64_t* edge_ptr;    /* device [G+1] */
+    const int64_t* edge_index;  /* device [2,E] contiguous: global ids within the call, edges grouped by graph */
+    int64_t E;                  /* edges of the call (the row length of edge_index) */
+    const int32_t* graph_ids;   /* device [n_ids] */
+    int32_t max_nodes, reserved;/* largest n this launch is sized for, 1 .. 128; 0 */
+    float* out;                 /* device [N] */
+    int32_t* status;            /* device [G] */
+} kpgnn_rd_desc;
+
+int kpgnn_resistance_distance(const kpgnn_rd_desc* d, kpgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The bodies' resistance-distance projection (csrc/rd_proj.hip; models/GNNs.py `x = x + self.rd_projection(rd)`, an
+ * nn.Linear(1, H)):   out[n,h] = x[n,h] + rd[n] * w[h] + b[h]                  one launch
+ * Backward: dx is dy itself (the caller returns it, nothing is launched); dw[h] = sum_n rd[n] dy[n,h], db[h] = sum_n dy[n,h]:
+ * per-block partial sums in DOUBLE in `workspace`, added in block order by a one-block finalize.  Row r always belongs to
+ * block (r / rows-per-block) mod 256 and a block without live rows contributes +0.0, so the sums do not depend on the
+ * capacity N, only on the live rows: no atomics, bitwise reproducible.  Rows at or beyond *n_dyn are not read, written or
+ * summed.  1 <= H <= 256 (KPGNN_EINVAL below, KPGNN_ELIMIT above); N == 0: fwd launches nothing, bwd writes zeros.
+ * `workspace` (kpgnn_rd_proj_workspace_bytes, 16-byte aligned) need not be zeroed.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct kpgnn_rd_proj_desc {
+    int64_t N; int32_t H, reserved;                /* rows (capacity with n_dyn), row width (1 .. 256); 0 */
+    const float* x; int64_t x_stride;              /* device [N,H], row stride in floats (>= H) (fwd) */
+    const float* rd;                               /* device [N] contiguous (both directions) */
+    const float* w; const float* b;                /* device [H] each (fwd) */
+    float* out; int64_t out_stride;                /* device [N,H] (fwd; may be x itself) */
+    /* backward only */
+    const float* dy; int64_t dy_stride;            /* device [N,H] */
+    float* dw; float* db;                          /* device [H] each */
+    void* workspace; size_t workspace_bytes;       /* >= kpgnn_rd_proj_workspace_bytes(N, H) */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= N; kpgnn_wgrad_desc explains); NULL: all N rows */
+} kpgnn_rd_proj_desc;
+
+/* 0 = the shape is not covered. */
+size_t kpgnn_rd_proj_workspace_bytes(int64_t N, int32_t H);
+int kpgnn_rd_proj_fwd(const kpgnn_rd_proj_desc* d, kpgnn_stream_t stream);
+int kpgnn_rd_proj_bwd(const kpgnn_rd_proj_desc* d, kpgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

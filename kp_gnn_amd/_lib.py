@@ -379,6 +379,28 @@ class NormDesc(ctypes.Structure):
     ]
 
 
+RD_OK, RD_ASYMMETRIC, RD_TOO_LARGE, RD_PIVOT, RD_RANGE = 0, 1, 2, 3, 4    # include/kpgnn.h KPGNN_RD_*
+RD_MAX_NODES, RD_WAVE_NODES = 128, 32                                   # KPGNN_RD_MAX_NODES, KPGNN_RD_WAVE_NODES
+RD_PROJ_MAX_H = 256                                                     # csrc/rd_proj.hip kMaxH
+
+
+class RdDesc(ctypes.Structure):
+    _fields_ = [
+        ("G", c_i32), ("n_ids", c_i32), ("node_ptr", c_vp), ("edge_ptr", c_vp), ("edge_index", c_vp), ("E", c_i64),
+        ("graph_ids", c_vp), ("max_nodes", c_i32), ("reserved", c_i32), ("out", c_vp), ("status", c_vp),
+    ]
+
+
+class RdProjDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("H", c_i32), ("reserved", c_i32),
+        ("x", c_vp), ("x_stride", c_i64), ("rd", c_vp), ("w", c_vp), ("b", c_vp), ("out", c_vp), ("out_stride", c_i64),
+        ("dy", c_vp), ("dy_stride", c_i64), ("dw", c_vp), ("db", c_vp),
+        ("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t),
+        ("n_dyn", c_vp),
+    ]
+
+
 class AttnPoolDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i64), ("G", c_i32), ("D", c_i32),
@@ -486,6 +508,10 @@ SIGNATURES = {
     "kpgnn_segment_pool_bwd": (ctypes.c_int, [ctypes.POINTER(PoolDesc), c_vp]),
     "kpgnn_segment_max_fwd": (ctypes.c_int, [ctypes.POINTER(PoolMaxDesc), c_vp]),
     "kpgnn_segment_max_bwd": (ctypes.c_int, [ctypes.POINTER(PoolMaxDesc), c_vp]),
+    "kpgnn_resistance_distance": (ctypes.c_int, [ctypes.POINTER(RdDesc), c_vp]),
+    "kpgnn_rd_proj_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i32]),
+    "kpgnn_rd_proj_fwd": (ctypes.c_int, [ctypes.POINTER(RdProjDesc), c_vp]),
+    "kpgnn_rd_proj_bwd": (ctypes.c_int, [ctypes.POINTER(RdProjDesc), c_vp]),
     "kpgnn_vn_add_pool": (ctypes.c_int, [ctypes.POINTER(VnDesc), c_vp]),
     "kpgnn_dropout_fwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
     "kpgnn_dropout_bwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),

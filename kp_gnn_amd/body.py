@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from .layers.gine import GINEConv
 from .ops import (DictPeripheral, attention_pool, body_norm, dropout_add, embedding_rows, enc_tables, jk_lstm_applies, jk_lstm_score,
                   jk_native_applies, jk_reduce,
-                  native_dropout_applies, refuse_dynamic_rows, segment_max, segment_pool, table_gather_sum, virtual_node_add)
+                  native_dropout_applies, rd_project, rd_project_applies, refuse_dynamic_rows, segment_max, segment_pool, table_gather_sum, virtual_node_add)
 from .ops_dense import (JKConcatLinear, batch_norm_act, head_linear, jk_concat_linear_nograd, mlp_linear_bn_relu_x2,
                         prepare_mlp_splits, score_head)
 
@@ -380,7 +380,13 @@ class _KHopBody(nn.Module):
         x = self.init_proj(data).squeeze()
         rd = _get(data, "rd")
         if self.use_rd and rd is not None:
-            x = x + self.rd_projection(rd).squeeze()
+            lin = self.rd_projection
+            if rd_project_applies(x, rd, lin.weight, lin.bias):     # fp32 device rows, H <= 256: one native launch
+                x = rd_project(x, rd, lin.weight, lin.bias)
+            else:
+                if x.is_cuda and x.dim() == 2:      # the framework Linear would sum its gradients over the dead rows too
+                    refuse_dynamic_rows("the framework rd_projection", x.shape[0])
+                x = x + lin(rd).squeeze()
         return x
 
     def _peripheral(self, data, num_nodes, like):

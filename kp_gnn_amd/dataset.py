@@ -64,9 +64,13 @@ class KHopDataset:
 
     # ------------------------------------------------------------------------------------------------ construction
     @staticmethod
-    def from_collated(batch, node_ptr, device, chunk_graphs=4096, with_entry_lists=True):
+    def from_collated(batch, node_ptr, device, chunk_graphs=4096, with_entry_lists=True, with_rd=False):
         """`batch`: a HOST KHopBatch holding ALL graphs collated (batch.collate_khop: the reference's pre_transform output in
-        PyG's concatenated layout); node_ptr [G+1] its slices.  The CSR is built chunk by chunk on the device."""
+        PyG's concatenated layout); node_ptr [G+1] its slices.  The CSR is built chunk by chunk on the device.
+        with_rd: also compute the resistance-distance node feature (`--use_rd`) per chunk with ops.resistance_distance from the
+        chunk's K-hop edge list, which is on the device anyway - the reference computes it AFTER its K-hop transform too
+        (train_qm9.py:241) - and keep it as node_rows["rd"] [Nd,1] float32, so that every collated batch has `.rd`.  A
+        `batch.rd` that is already there is carried as given, whatever with_rd says."""
         if batch.edge_index.is_cuda:
             raise ValueError("from_collated expects the host-side collated dataset")
         ds = KHopDataset()
@@ -92,12 +96,17 @@ class KHopDataset:
         pair_cnt, ent_cnt, hop_cnt = [], [], []
         max0 = maxk = 0
         dev = ds.device
+        given_rd = getattr(batch, "rd", None)
+        rd_parts = [] if (with_rd and given_rd is None) else None
         for g0 in range(0, G, chunk_graphs):
             g1 = min(G, g0 + chunk_graphs)
             n0, n1, e0, e1 = int(node_ptr[g0]), int(node_ptr[g1]), int(edge_ptr[g0]), int(edge_ptr[g1])
             Nc = n1 - n0
             cei = (ei[:, e0:e1] - n0).to(dev)
             cea = ea[e0:e1].to(dev)
+            if rd_parts is not None:
+                from .ops import resistance_distance
+                rd_parts.append(resistance_distance(node_ptr[g0:g1 + 1] - n0, edge_ptr[g0:g1 + 1] - e0, cei, dev)[0])
             csr = KHopCSR.build(cei, cea, Nc, nodes_per_tile=1 if with_entry_lists else None)
             max0, maxk = max(max0, csr.max_code0), max(maxk, csr.max_codek)
             nptr = torch.from_numpy(node_ptr[g0:g1 + 1] - n0).to(dev)                 # [gc+1] chunk-local node offsets
@@ -154,6 +163,10 @@ class KHopDataset:
                 ds.node_rows["x"] = x.to(dev).contiguous()
         if getattr(batch, "z", None) is not None:
             ds._add_index_rows("z", batch.z)
+        if given_rd is not None:
+            ds.node_rows["rd"] = given_rd.to(device=dev, dtype=torch.float32).reshape(Nd, 1).contiguous()
+        elif rd_parts is not None:
+            ds.node_rows["rd"] = torch.cat(rd_parts) if rd_parts else torch.zeros((0, 1), dtype=torch.float32, device=dev)
         if batch.y is not None:
             ds.graph_rows["y"] = batch.y.to(dev).contiguous()
         pea, pca = batch.peripheral_edge_attr, batch.peripheral_configuration_attr

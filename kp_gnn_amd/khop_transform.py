@@ -138,6 +138,40 @@ def extract_multi_hop_neighbors(data, K, max_edge_attr_num, max_hop_num, max_edg
     return data
 
 
+def resistance_distance_host(n, edge_index):
+    """Resistance distance of every node to node 0, float64 numpy [n] (reference data_utils.py:280-303, restated without scipy):
+    A the summed adjacency of `edge_index` [2,E] (ones; duplicates add) with its diagonal cleared - scipy's csgraph.laplacian
+    ignores self-loops -, L = diag(column sums of A) - A as its default (in-degree) form gives it, L+ = pinv(L), and
+    rd[y] = ((L+[0,0] + L+[y,y]) - L+[0,y]) - L+[y,0], so rd[0] is exactly 0.  Any edge list, directed ones included; this is
+    what the device route falls back to for the graphs its kernel does not serve."""
+    n = int(n)
+    if n == 0:
+        return np.zeros(0, dtype=np.float64)
+    ei = np.asarray(edge_index.cpu() if torch.is_tensor(edge_index) else edge_index, dtype=np.int64).reshape(2, -1)
+    if ei.size and (ei.min() < 0 or ei.max() >= n):
+        raise IndexError(f"edge endpoint outside [0, {n})")
+    A = np.zeros((n, n), dtype=np.float64)
+    np.add.at(A, (ei[0], ei[1]), 1.0)
+    np.fill_diagonal(A, 0.0)
+    Lp = np.linalg.pinv(np.diag(A.sum(axis=0)) - A)
+    return ((Lp[0, 0] + np.diagonal(Lp)) - Lp[0, :]) - Lp[:, 0]
+
+
+def resistance_distance(data):
+    """Same contract as the reference's data_utils.resistance_distance (:280-303): sets `data.rd` [num_nodes, 1] float32 from
+    `data.edge_index` / `data.num_nodes` and returns `data`.  The feature follows the edge list it is handed - after the K-hop
+    transform that is the K-hop edge list, as in the reference's pipeline.  A device `edge_index` takes the batched kernel
+    (ops.resistance_distance, one graph), a host one the float64 route above; `rd` lands where `edge_index` lives."""
+    edge_index = data.edge_index
+    num_nodes = data.num_nodes if getattr(data, "num_nodes", None) is not None else data.x.size(0)
+    if edge_index.is_cuda:
+        from .ops import resistance_distance as rd_device
+        data.rd = rd_device([0, num_nodes], [0, edge_index.size(1)], edge_index, edge_index.device)[0]
+    else:
+        data.rd = torch.from_numpy(resistance_distance_host(num_nodes, edge_index).astype(np.float32)).unsqueeze(1)
+    return data
+
+
 class SynthShape(ctypes.Structure):
     """kpgnn_synth_shape (include/kpgnn_host.h)."""
     _fields_ = [("mean_nodes", ctypes.c_double), ("std_nodes", ctypes.c_double), ("min_nodes", ctypes.c_int32),

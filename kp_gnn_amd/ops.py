@@ -3,6 +3,7 @@ and strides out; every arithmetic step of the K-hop aggregation runs in the HIP 
 import collections
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2141,6 +2142,167 @@ def body_norm(x, kind, weight=None, bias=None, residual=None, eps=1e-5):
     if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (x, weight, bias, residual)):
         return _norm_fwd_launch(x.detach(), kind, weight, bias, residual, eps)[0]      # no autograd node, nothing saved
     return BodyNorm.apply(x, weight, bias, residual, kind, eps)
+
+
+# ------------------------------------------------------------------------------------------------ resistance distance
+def _host_i64(a):
+    return np.ascontiguousarray(np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.int64)).reshape(-1)
+
+
+def resistance_distance(node_ptr, edge_ptr, edge_index, device):
+    """The reference's `rd` node feature (data_utils.py:280-303) of G graphs at once: (rd [N,1] float32 on `device`, status
+    [G] int32 on the host).  node_ptr / edge_ptr [G+1]: host offsets of each graph's nodes and edges; edge_index [2,E] int64
+    (host or device): ids global within the call, edges grouped by graph.  The graphs are bucketed by size on the host, one
+    kpgnn_resistance_distance launch per class (n <= 32: a wavefront per graph; n <= 128: a block per graph), and `status` is
+    read back once.  It tells which graphs the kernel served (0); those it did not - a directed list (1), more than 128
+    nodes (2), a failed pivot (3) - are filled from khop_transform.resistance_distance_host, and an edge endpoint outside
+    its graph (4) raises IndexError before anything else is launched or filled."""
+    node_ptr, edge_ptr = _host_i64(node_ptr), _host_i64(edge_ptr)
+    G = node_ptr.shape[0] - 1
+    if G < 0 or edge_ptr.shape[0] != G + 1:
+        raise ValueError("node_ptr and edge_ptr must both have G + 1 entries")
+    if node_ptr[0] != 0 or edge_ptr[0] != 0 or bool((np.diff(node_ptr) < 0).any()) or bool((np.diff(edge_ptr) < 0).any()):
+        raise ValueError("node_ptr / edge_ptr must start at 0 and not decrease")
+    N, E = int(node_ptr[-1]), int(edge_ptr[-1])
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.shape[1] != E:
+        raise ValueError("edge_index does not match edge_ptr")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.KpgnnError("ops.resistance_distance is the device route: khop_transform.resistance_distance_host is the host one")
+    out = torch.zeros((N, 1), dtype=torch.float32, device=dev)
+    status = np.zeros(G, dtype=np.int32)
+    if G == 0:
+        return out, torch.from_numpy(status)
+    ei = edge_index.to(device=dev, dtype=torch.int64).contiguous()
+    nptr, eptr = torch.from_numpy(node_ptr).to(dev), torch.from_numpy(edge_ptr).to(dev)
+    st = torch.empty(G, dtype=torch.int32, device=dev)
+    nodes = np.diff(node_ptr)
+    keep = []
+    for ids in (np.flatnonzero(nodes <= _lib.RD_WAVE_NODES), np.flatnonzero(nodes > _lib.RD_WAVE_NODES)):
+        if ids.size == 0:
+            continue
+        ids_d = torch.from_numpy(ids.astype(np.int32)).to(dev)
+        keep.append(ids_d)
+        d = _lib.RdDesc()
+        d.G, d.n_ids, d.E = G, ids.size, E
+        d.node_ptr, d.edge_ptr, d.edge_index, d.graph_ids = nptr.data_ptr(), eptr.data_ptr(), ei.data_ptr(), ids_d.data_ptr()
+        d.max_nodes = max(1, min(_lib.RD_MAX_NODES, int(nodes[ids].max())))     # (larger graphs get status 2 from the kernel)
+        d.out, d.status = out.data_ptr(), st.data_ptr()
+        _lib.launch("kpgnn_resistance_distance", dev, ctypes.byref(d))
+    status = st.cpu()
+    del keep
+    bad = status.numpy()
+    if bool((bad == _lib.RD_RANGE).any()):
+        g = int(np.flatnonzero(bad == _lib.RD_RANGE)[0])
+        raise IndexError(f"graph {g}: an edge endpoint lies outside its nodes [{node_ptr[g]}, {node_ptr[g + 1]})")
+    todo = np.flatnonzero(bad != 0)
+    if todo.size:
+        from .khop_transform import resistance_distance_host
+        ei_h = edge_index.cpu() if edge_index.is_cuda else edge_index
+        ei_h = ei_h.numpy()
+        rows, vals = [], []
+        for g in todo:
+            n0, n1, e0, e1 = node_ptr[g], node_ptr[g + 1], edge_ptr[g], edge_ptr[g + 1]
+            rows.append(np.arange(n0, n1))
+            vals.append(resistance_distance_host(n1 - n0, ei_h[:, e0:e1] - n0).astype(np.float32))
+        out[torch.from_numpy(np.concatenate(rows)).to(dev), 0] = torch.from_numpy(np.concatenate(vals)).to(dev)
+    return out, status
+
+
+# ------------------------------------------------------------------------------------------------ the rd projection
+# x + rd_projection(rd) of the bodies (models/GNNs.py; kpgnn.h, kpgnn_rd_proj_desc): one launch forward; backward dx is the
+# incoming gradient and dw / db are two launches of double partial sums over the LIVE rows - the framework's Linear(1, H)
+# sums its weight and bias gradients over every row of a capacity-shaped batch, uninitialised dead ones included.
+_NATIVE_RD_PROJ = True
+
+
+def set_native_rd_proj(on):
+    """Route the bodies' rd projection of fp32 device rows through kpgnn_rd_proj_* (True) or keep the framework expression
+    x + Linear(rd) on exact-shape batches (False).  Inside a dynamic_rows block it is native whatever this says: it is the
+    only route there.  Returns the previous setting."""
+    global _NATIVE_RD_PROJ
+    prev, _NATIVE_RD_PROJ = _NATIVE_RD_PROJ, bool(on)
+    return prev
+
+
+def native_rd_proj():
+    return _NATIVE_RD_PROJ
+
+
+def _rd_proj_covers(x, rd, w, b):
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and 1 <= x.shape[1] <= _lib.RD_PROJ_MAX_H):
+        return False
+    N, H = x.shape
+    ok = rd.is_cuda and rd.dtype == torch.float32 and rd.dim() in (1, 2) and rd.numel() == N and not rd.requires_grad
+    ok = ok and w.is_cuda and w.dtype == torch.float32 and tuple(w.shape) == (H, 1)
+    return bool(ok and b is not None and b.is_cuda and b.dtype == torch.float32 and tuple(b.shape) == (H,))
+
+
+def rd_project_applies(x, rd, w, b):
+    """Whether rd_project takes the native route: fp32 device rows x [N,H] with N >= 1 and H <= 256, rd [N,1] or [N] without
+    a gradient of its own, w [H,1], b [H] - and the switch is on or a dynamic_rows block over N rows is active."""
+    return _rd_proj_covers(x, rd, w, b) and (_NATIVE_RD_PROJ or dyn_ptr(x.shape[0]) is not None)
+
+
+def rd_project_reference(x, rd, w, b):
+    """The framework expression x + Linear(rd) evaluated in float64 (any device): what the tests hold the kernels to."""
+    return x.double() + torch.nn.functional.linear(rd.double().reshape(-1, 1), w.double(), b.double())
+
+
+def _rd_proj_fwd_launch(x, rd, w, b):
+    N, H = x.shape
+    x = _rows_view(x, H)
+    out = torch.empty((N, H), dtype=torch.float32, device=x.device)
+    w, b = w.reshape(-1).contiguous(), b.contiguous()
+    d = _lib.RdProjDesc()
+    d.N, d.H, d.n_dyn = N, H, dyn_ptr(N)
+    d.x, d.x_stride, d.rd, d.w, d.b, d.out, d.out_stride = x.data_ptr(), x.stride(0), rd.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), H
+    _lib.launch("kpgnn_rd_proj_fwd", x.device, ctypes.byref(d))
+    return out
+
+
+class RdProject(torch.autograd.Function):
+    """out = x + rd w^T + b (kpgnn_rd_proj_fwd); backward: x gets the incoming gradient itself, w and b theirs from one
+    kpgnn_rd_proj_bwd call (live rows only, no atomics).  Only rd is kept."""
+
+    @staticmethod
+    def forward(ctx, x, rd, w, b):
+        rd = rd.reshape(-1).contiguous()
+        ctx.save_for_backward(rd)
+        return _rd_proj_fwd_launch(x, rd, w, b)
+
+    @staticmethod
+    def backward(ctx, gout):
+        (rd,) = ctx.saved_tensors
+        N, H = gout.shape
+        need_x, _, need_w, need_b = ctx.needs_input_grad
+        dw = db = None
+        if need_w or need_b:
+            dy = _rows_view(gout, H)
+            dw = torch.empty((H, 1), dtype=torch.float32, device=gout.device)
+            db = torch.empty(H, dtype=torch.float32, device=gout.device)
+            nbytes = _lib.load().kpgnn_rd_proj_workspace_bytes(N, H)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=gout.device)
+            d = _lib.RdProjDesc()
+            d.N, d.H, d.n_dyn = N, H, dyn_ptr(N)
+            d.rd, d.dy, d.dy_stride, d.dw, d.db = rd.data_ptr(), dy.data_ptr(), dy.stride(0), dw.data_ptr(), db.data_ptr()
+            d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
+            _lib.launch("kpgnn_rd_proj_bwd", gout.device, ctypes.byref(d))
+            del ws
+        return gout if need_x else None, None, dw if need_w else None, db if need_b else None
+
+
+def rd_project(x, rd, w, b):
+    """x + rd_projection(rd) for the Linear(1, H) parameters w [H,1], b [H].  Where rd_project_applies: one kpgnn_rd_proj_fwd
+    launch, live rows only inside a dynamic_rows block (rows beyond them are left alone).  Everything else - CPU tensors,
+    other dtypes, H > 256, the switch off - keeps the framework expression, which has no dynamic row count and refuses one."""
+    if not rd_project_applies(x, rd, w, b):
+        if x.is_cuda and x.dim() == 2:
+            refuse_dynamic_rows("the framework expression of the rd projection", x.shape[0])
+        return x + torch.nn.functional.linear(rd, w, b).squeeze()
+    if not torch.is_grad_enabled() or not any(t.requires_grad for t in (x, w, b)):
+        return _rd_proj_fwd_launch(x.detach(), rd.reshape(-1).contiguous(), w, b)
+    return RdProject.apply(x, rd, w, b)
 
 
 class AttentionPool(torch.autograd.Function):
