@@ -830,7 +830,8 @@ int kpgnn_bn_eval(const kpgnn_bn_eval_desc* d, kpgnn_stream_t stream);
  * Graph readout over a collated batch (models/GraphRegression.py:46-51: PyG global_add_pool / global_mean_pool):
  *   out[g,:] = sum (mode 0) or mean (mode 1) of x[n,:] over the nodes n of graph g;  gx[n,:] = gout[batch[n],:] (/ count)
  * The nodes of a graph are contiguous (graph_ptr[g] .. graph_ptr[g+1]), rows are added in node order: bitwise
- * reproducible, unlike a scatter with fp32 atomics.  One launch per direction.
+ * reproducible, unlike a scatter with fp32 atomics.  One launch per direction.  Rows at or beyond the live count are
+ * never read, and the mean divides by a graph's live rows in both directions, even where graph_ptr runs past the count.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct kpgnn_pool_desc {
     int64_t N;                  /* nodes */

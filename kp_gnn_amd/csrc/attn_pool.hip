@@ -3,7 +3,7 @@
 // (models/GraphClassification.py:31-32,51; train_graph_property.py:149 makes it the default readout), which the framework
 // runs as a [N,H] x [H,1] library GEMM, a scatter-max, a gather, an exp, a scatter-add with fp32 atomics, a divide, a
 // multiply and a second atomic scatter-add, and as many again in backward.  Collated batches keep the nodes of a graph
-// contiguous, so, as in pool.hip, a sub-group of lanes owns one graph and its lanes span the feature columns.  Forward:
+// contiguous, so, as in segment_rows.h, a sub-group of lanes owns one graph and its lanes span the feature columns.  Forward:
 // ONE pass over the graph's rows with a running maximum (gate, online max / sum of exponentials and the weighted row sum
 // all come from the one load of x[n,:]); the gates are parked in alpha[] and turned into weights by a second pass over
 // those N floats only.  Backward: the same walk gives gx and per-graph sums of dgate[n] x[n,:]; the sub-groups of a block meet
@@ -11,14 +11,12 @@
 // bitwise reproducible.
 // The lane-group-per-graph shape is tuned for collated molecule-size graphs (tens of nodes, hundreds of graphs); the
 // result is correct for any graph size, but one graph of many thousand nodes is walked by a single sub-group.
-#include <initializer_list>
-
-#include "kpgnn_common.h"
+#include "segment_rows.h"
 
 namespace kpgnn {
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kRowBlock;
 constexpr int kMaxD = 256;
 
 struct AttnPoolParams {
@@ -35,19 +33,6 @@ struct AttnPoolParams {
 // Chunks of L * VEC columns a lane walks: sub-groups stay inside a wave (L <= 64), so rows wider than 64 * VEC take several.
 template <int VEC, int L> constexpr int chunks() { return L < 64 ? 1 : (VEC == 4 ? 1 : (VEC == 2 ? 2 : 4)); }
 
-template <int L> __device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int o = L >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// The live node range of graph g: graph_ptr clamped to the live row count, so that no row at or beyond it is touched.
-__device__ __forceinline__ void graph_range(const AttnPoolParams& p, int64_t g, int64_t N, int* beg, int* end) {
-    const int64_t b = p.ptr[g], e = p.ptr[g + 1];
-    *beg = (int)(b < N ? (b < 0 ? 0 : b) : N);
-    *end = (int)(e < N ? e : N);
-}
-
 template <int VEC, int L>
 __global__ void __launch_bounds__(kBlock) attn_pool_fwd_kernel(AttnPoolParams p) {
     constexpr int NCH = chunks<VEC, L>();
@@ -55,8 +40,8 @@ __global__ void __launch_bounds__(kBlock) attn_pool_fwd_kernel(AttnPoolParams p)
     const int sg = threadIdx.x / L, sl = threadIdx.x % L;
     const int64_t g = (int64_t)blockIdx.x * (kBlock / L) + sg;
     if (g >= p.G) return;                                     // (whole sub-groups leave: the shuffles below stay inside one)
-    int beg, end;
-    graph_range(p, g, N, &beg, &end);
+    const GraphRows rows = graph_rows(p.ptr, g, N);
+    const int beg = rows.beg, end = rows.end;
     const float b0 = p.bias ? p.bias[0] : 0.f;
     float w[NCH][VEC], acc[NCH][VEC];
     bool on[NCH];
@@ -124,8 +109,8 @@ __global__ void __launch_bounds__(kBlock) attn_pool_bwd_kernel(AttnPoolParams p)
     for (int j = 0; j < NCH; ++j)
         for (int q = 0; q < VEC; ++q) dwa[j][q] = 0.f;
     if (g < p.G) {
-        int beg, end;
-        graph_range(p, g, N, &beg, &end);
+        const GraphRows rows = graph_rows(p.ptr, g, N);
+        const int beg = rows.beg, end = rows.end;
         float w[NCH][VEC], go[NCH][VEC];
         bool on[NCH];
         float sdot = 0.f;
@@ -207,8 +192,6 @@ int shape(int D, std::initializer_list<const void*> ptrs, std::initializer_list<
     return KPGNN_OK;
 }
 
-int grid_of(int G, int lanes) { return (G + (kBlock / lanes) - 1) / (kBlock / lanes); }
-
 int check(const kpgnn_attn_pool_desc* d, const char* who) {
     KPGNN_REQUIRE(d != nullptr, "%s: NULL descriptor", who);
     KPGNN_REQUIRE(d->N >= 0 && d->G >= 0 && d->D >= 1, "%s: bad N=%lld G=%d D=%d", who, (long long)d->N, d->G, d->D);
@@ -227,7 +210,7 @@ extern "C" size_t kpgnn_attn_pool_workspace_bytes(int32_t G, int32_t D) {
     if (G < 1 || D < 1 || D > kMaxD) return 0;
     int lanes = row_lanes(D, 1);                              // the fewest graphs per block any row shape gives
     if (lanes > kWave) lanes = kWave;
-    return (size_t)grid_of(G, lanes) * (size_t)(D + 1) * sizeof(float);
+    return (size_t)graph_grid(G, lanes) * (size_t)(D + 1) * sizeof(float);
 }
 
 extern "C" int kpgnn_attn_pool_fwd(const kpgnn_attn_pool_desc* d, kpgnn_stream_t stream) {
@@ -241,7 +224,7 @@ extern "C" int kpgnn_attn_pool_fwd(const kpgnn_attn_pool_desc* d, kpgnn_stream_t
     p.n_dyn = d->n_dyn; p.N = d->N; p.G = d->G; p.D = d->D; p.ptr = d->graph_ptr; p.x = d->x; p.xs = d->x_stride;
     p.w = d->w; p.bias = d->bias; p.alpha = d->alpha; p.out = d->out;
     hipStream_t s = (hipStream_t)stream;
-    const unsigned grid = (unsigned)grid_of(d->G, lanes);
+    const unsigned grid = graph_grid(d->G, lanes);
     return dispatch_row_shape<64>(vec, lanes, "attn_pool_fwd", [&](auto V, auto L) {
         hipLaunchKernelGGL((attn_pool_fwd_kernel<V.value, L.value>), dim3(grid), dim3(kBlock), 0, s, p);
         KPGNN_LAUNCH_CHECK("attn_pool_fwd_kernel");
@@ -257,7 +240,7 @@ extern "C" int kpgnn_attn_pool_bwd(const kpgnn_attn_pool_desc* d, kpgnn_stream_t
     rc = shape(d->D, {d->x, d->w, d->out, d->gout, d->gx}, {d->x_stride, d->gx ? d->gx_stride : 0}, &vec, &lanes);
     if (rc != KPGNN_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int grid = d->G > 0 ? grid_of(d->G, lanes) : 0;
+    const int grid = (int)graph_grid(d->G, lanes);
     if (grid == 0) {                                          // no graph: the parameter gradients are zero
         KPGNN_HIP_TRY(hipMemsetAsync(d->dw, 0, sizeof(float) * d->D, s));
         if (d->db) KPGNN_HIP_TRY(hipMemsetAsync(d->db, 0, sizeof(float), s));

@@ -4,10 +4,8 @@
 // models/GNNs.py:103-112 builds one PyG norm per layer from --norm_type and calls it without a batch vector, so the whole batch
 // is one graph.  All four, in both directions, are the same three steps: two column sums over the live rows (x and x^2 forward,
 // gout and gout * x backward), a handful of per-column coefficients derived from them, and one streaming pass over the rows.
-//   1. norm_stats_kernel: a group of G lanes owns a row, VEC columns per lane (the shared row shapes); every thread sums its
-//      columns over the block's rows in DOUBLE (a product of two fp32 values is exact there), the block adds its row groups in
-//      group order and writes one partial double[2][C].  EVERY block writes its partial, zeros included, so the workspace need
-//      not be cleared and a block whose rows all lie beyond the live count contributes exactly nothing.
+//   1. norm_stats_kernel: the statistics block of column_stats.h, one partial double[2][C] per block; block b owns the rows
+//      b * R + group, then every gridDim.x * R rows.
 //   2. norm_finalize_kernel: one block adds the partials in block order (contiguous slices of blocks, slices in order), reads the
 //      live row count on the device, and leaves fp32 coefficients: `saved` forward, a [5][C] table in the workspace backward.
 //   3. norm_apply_kernel: out = (x - m[c]) * s[c] * w[c] + b[c] (+ residual) forward, gx = P[c] (g - Gm[c]) + K[c] (x - m[c]) +
@@ -15,20 +13,16 @@
 //      rounding noise scaled by 1 / sqrt(eps) = 316 where the answer is exactly 0.
 // GraphSize needs no sums: one launch that reads the live count itself.  No atomics anywhere: the same inputs at the same
 // capacity give the same bits.  Bound by bytes: 4 N C read per statistics pass and 8 .. 12 N C moved per apply pass.
-#include "kpgnn_common.h"
+#include "column_stats.h"
 
 #include <cmath>
 
 namespace kpgnn {
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kRowBlock;
 constexpr int kMaxC = 256;           // a row fits one pass of the widest row shape, and one finalize thread per column
 constexpr int kStatRows = 32;        // capacity rows per statistics block until the grid stops growing
-constexpr int kMaxStatGrid = 256;    // one block per CU: the finalize block reads P * 16 C bytes of partials alone
-constexpr int kFinBlock = 1024;
-constexpr int kMaxSlices = 16;
-constexpr int kMaxApplyGrid = 2048;  // 256 CUs x 8 blocks: grid-stride beyond
 constexpr int kCoef = 5;             // backward coefficient rows: m, P, Gm, K, D
 
 enum { APPLY_FWD = 0, APPLY_BWD = 1, APPLY_SCALE = 2 };
@@ -49,58 +43,14 @@ struct NormParams {
 
 template <int BWD, int VEC, int G>
 __global__ void __launch_bounds__(kBlock) norm_stats_kernel(const NormParams p) {
-    constexpr int R = kBlock / G, W = G * VEC;          // rows per pass; columns a pass spans (>= C)
-    __shared__ double sm[2 * kBlock * VEC];             // [2][R][W]
-    const int64_t n = live_rows(p.N, p.n_dyn);
-    const int lane = threadIdx.x % G, rg = threadIdx.x / G, c0 = lane * VEC;
-    double a0[VEC], a1[VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) a0[j] = a1[j] = 0.0;
-    if (c0 < p.C) {
-        const int64_t step = (int64_t)gridDim.x * R;
-        int64_t row = (int64_t)blockIdx.x * R + rg;
-        for (; row + 3 * step < n; row += 4 * step) {      // four rows' loads in flight, added in row order
-            float v[4][VEC], u[4][VEC];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                ldv<VEC>(p.x + (row + q * step) * p.xs + c0, v[q]);
-                if (BWD) ldv<VEC>(p.g + (row + q * step) * p.gs + c0, u[q]);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) {
-                    const double xv = (double)v[q][j], f = BWD ? (double)u[q][j] : xv;
-                    a0[j] += f;
-                    a1[j] = fma(f, xv, a1[j]);
-                }
-        }
-        for (; row < n; row += step) {
-            float v[VEC], u[VEC];
-            ldv<VEC>(p.x + row * p.xs + c0, v);
-            if (BWD) ldv<VEC>(p.g + row * p.gs + c0, u);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                const double xv = (double)v[j], f = BWD ? (double)u[j] : xv;
-                a0[j] += f;
-                a1[j] = fma(f, xv, a1[j]);
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-        sm[(0 * R + rg) * W + c0 + j] = a0[j];
-        sm[(1 * R + rg) * W + c0 + j] = a1[j];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < p.C) {
-        const int c = threadIdx.x;
-        double t0 = 0.0, t1 = 0.0;
-        for (int q = 0; q < R; ++q) { t0 += sm[(0 * R + q) * W + c]; t1 += sm[(1 * R + q) * W + c]; }
-        double* dst = p.part + (int64_t)blockIdx.x * 2 * p.C;
-        dst[c] = t0;
-        dst[p.C + c] = t1;
-    }
+    const int c0 = (int)(threadIdx.x % G) * VEC;
+    // f = m = x forward (sum x, sum x^2); f = gout, m = x backward (sum g, sum g x)
+    column_stats_block<VEC, G>(live_rows(p.N, p.n_dyn), (int64_t)gridDim.x * (kBlock / G), p.C, p.part,
+                               [&](int64_t row, float (&f)[VEC], float (&m)[VEC]) {
+        ldv<VEC>(p.x + row * p.xs + c0, m);
+        if (BWD) ldv<VEC>(p.g + row * p.gs + c0, f);
+        else for (int j = 0; j < VEC; ++j) f[j] = m[j];
+    });
 }
 
 // red[0][0], red[1][0] = the sums of red[0][0 .. 255], red[1][0 .. 255] in a fixed tree; every thread of the block calls
@@ -266,13 +216,8 @@ __global__ void __launch_bounds__(kBlock) norm_apply_kernel(const NormParams p) 
     }
 }
 
-int stat_grid(int64_t N) {
-    const int64_t b = (N + kStatRows - 1) / kStatRows;
-    return (int)(b < 1 ? 1 : (b > kMaxStatGrid ? kMaxStatGrid : b));
-}
-
 size_t workspace_bytes(int64_t N, int C) {
-    const size_t b = (size_t)stat_grid(N) * 2 * C * sizeof(double) + (size_t)kCoef * C * sizeof(float);
+    const size_t b = (size_t)stat_blocks(N, kStatRows) * 2 * C * sizeof(double) + (size_t)kCoef * C * sizeof(float);
     return (b + 15) & ~(size_t)15;
 }
 
@@ -297,7 +242,7 @@ NormParams params_of(const kpgnn_norm_desc* d) {
     p.x = d->x; p.xs = d->x_stride;
     if (d->kind == KPGNN_NORM_LAYER) { p.w = d->weight; p.b = d->bias; }
     p.saved = d->saved;
-    p.P = stat_grid(d->N);
+    p.P = stat_blocks(d->N, kStatRows);
     p.part = reinterpret_cast<double*>(d->workspace);
     p.coef = reinterpret_cast<float*>(p.part + (size_t)p.P * 2 * d->C);
     return p;

@@ -77,7 +77,7 @@ __global__ void __launch_bounds__(kLossBlock) nll_loss_kernel(LossParams p) {
         }
         float se = 0.f;
         for (int c = sl; c < C; c += L) se += expf(row[c] - mx);
-        for (int o = L >> 1; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+        se = group_sum(se, L);
         const float lt = row[t];
         if (sl == 0) {
             lsum += (logf(se) + mx) - lt;

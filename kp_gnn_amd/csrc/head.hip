@@ -18,7 +18,7 @@ score_head_fwd_kernel(const float* __restrict__ pooled, const float* __restrict_
     if (g >= G) return;
     float s = 0.f;
     for (int c = lane; c < D; c += 64) s = fmaf(pooled[g * D + c], w[c], s);
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = group_sum<64>(s);
     if (lane == 0) score[g] = s + (bias ? bias[0] : 0.f);
 }
 

@@ -36,12 +36,6 @@ struct HeadParams {
     int64_t rows_per_block;
 };
 
-template <int L> __device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int o = L >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <int VEC, int L>
 __global__ void __launch_bounds__(kBlock) head_linear_fwd_kernel(HeadParams p) {
     extern __shared__ __align__(16) float wl[];               // W [O][I]

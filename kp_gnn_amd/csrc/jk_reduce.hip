@@ -194,12 +194,6 @@ __device__ __forceinline__ float jk_softmax_bwd_slot(const JkParams& p, const fl
     return part;
 }
 
-// sum over the 1 << lanes_log2 lanes of a row (a butterfly: every lane ends with the same bits); a row never leaves its wave
-__device__ __forceinline__ float row_sum(float v, int lanes) {
-    for (int off = lanes >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
-
 template <int VEC>
 __global__ void __launch_bounds__(kBlock) jk_softmax_bwd_kernel(const JkParams p) {
     const int64_t n = live_rows(p.N, p.n_dyn);
@@ -231,7 +225,7 @@ __global__ void __launch_bounds__(kBlock) jk_softmax_bwd_kernel(const JkParams p
             for (int u = 0; u < kUnroll; ++u) {
                 const float part = jk_softmax_bwd_slot<VEC>(p, p.x[l + u], p.gx + (l + u) * block, row, lane, lanes, wl[u], g0,
                                                             v[u], have0);
-                const float d = row_sum(part, lanes);
+                const float d = group_sum(part, lanes);      // (the 1 << lanes_log2 lanes of a row never leave its wave)
                 dot = fmaf(wl[u], d, dot);
                 if (lane == 0) gsrow[l + u] = d;       // parked until the row's dot is known (below)
             }
@@ -243,7 +237,7 @@ __global__ void __launch_bounds__(kBlock) jk_softmax_bwd_kernel(const JkParams p
             if (have0) ldv<VEC>(p.x[l] + x0, v);
             const float wl = wrow[l];
             const float part = jk_softmax_bwd_slot<VEC>(p, p.x[l], p.gx + l * block, row, lane, lanes, wl, g0, v, have0);
-            const float d = row_sum(part, lanes);
+            const float d = group_sum(part, lanes);
             dot = fmaf(wl, d, dot);
             if (lane == 0) gsrow[l] = d;
         }

@@ -54,6 +54,18 @@ __device__ __forceinline__ T live_rows(T N, const int32_t* n_dyn) {
 }
 constexpr int kNumXcd = 8;  // MI355X: 8 XCDs, blocks are dealt round-robin over them
 
+// Sum over the L lanes of a sub-group (L a power of two <= 64, the sub-group aligned to L lanes): a butterfly with the offsets
+// L/2, L/4, ..., 1, so every lane ends with the same bits and the sum never leaves the sub-group's wave.
+template <int L> __device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+    for (int o = L >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+    return v;
+}
+__device__ __forceinline__ float group_sum(float v, int lanes) {      // the same butterfly for a run-time lane count
+    for (int o = lanes >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+    return v;
+}
+
 struct DeviceFacts {
     int cu_count = 256;
     int lds_per_block = 160 * 1024;
@@ -335,6 +347,7 @@ int dispatch_row_shape(int vec, int g, const char* who, F&& f) {
 #undef KPGNN_ROW_CASE
     return fail(KPGNN_EINVAL, "%s: no kernel for vec=%d g=%d", who, vec, g);
 }
+constexpr int kRowBlock = 256;      // threads of a block of the kernels behind segment_rows.h and column_stats.h
 // G alone from the same table, for kernels whose VEC is not this table's business: f(std::integral_constant<int, G>)
 template <int MAXG, typename F>
 int dispatch_row_lanes(int g, const char* who, F&& f) {

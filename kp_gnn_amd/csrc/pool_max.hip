@@ -2,17 +2,13 @@
 // backward that hands each winner its column's gradient (gfx950).  Contract: include/kpgnn.h, kpgnn_segment_max_fwd / _bwd.
 // Replaces PyG 2.1.0's global_max_pool = torch_scatter.scatter_max (models/GraphClassification.py:24-34), which the framework
 // restates as a -inf fill + an atomic-max scatter over an expanded [N,D] int64 index and whose backward splits a tied
-// column's gradient evenly.  Same mapping as pool.hip: a sub-group of lanes owns one graph, lanes span the feature columns
+// column's gradient evenly.  The walk of segment_rows.h: a sub-group of lanes owns one graph, lanes span the feature columns
 // 16 B wide, rows are compared in node order with a strict >, so the LOWEST row that attains the max wins - one winner per
 // (graph, column), bitwise reproducible, one launch per direction, no fill and no atomics.
-#include <initializer_list>
-
-#include "kpgnn_common.h"
+#include "segment_rows.h"
 
 namespace kpgnn {
 namespace {
-
-constexpr int kBlock = 256;
 
 struct MaxParams {
     const int32_t* n_dyn;
@@ -47,25 +43,27 @@ __device__ __forceinline__ void take(float (&acc)[VEC], int (&arg)[VEC], const f
 }
 
 template <int VEC, int L>
-__global__ void __launch_bounds__(kBlock) pool_max_fwd_kernel(MaxParams p) {
+__global__ void __launch_bounds__(kRowBlock) pool_max_fwd_kernel(MaxParams p) {
     p.N = live_rows(p.N, p.n_dyn);
     const int sg = threadIdx.x / L, sl = threadIdx.x % L, c0 = sl * VEC;
-    const int64_t g = (int64_t)blockIdx.x * (kBlock / L) + sg;
+    const int64_t g = (int64_t)blockIdx.x * (kRowBlock / L) + sg;
     if (g >= p.G || c0 >= p.D) return;
-    const int beg = p.ptr[g];
-    const int end = (int64_t)p.ptr[g + 1] < p.N ? p.ptr[g + 1] : (int)p.N;      // rows at or beyond the live count are never read
+    const GraphRows rows = graph_rows(p.ptr, g, p.N);       // rows at or beyond the live count are never read
     float acc[VEC];
     int arg[VEC];
     for (int q = 0; q < VEC; ++q) { acc[q] = -INFINITY; arg[q] = -1; }
-    int r = beg;
-    for (; r + 3 < end; r += 4) {             // four independent row loads per trip, compared in row order
+    // The walk of for_graph_rows, written out: handed `take` as a callable (a lambda, a functor, state by reference or by
+    // value), the compiler keeps its conditional stores as a branch per column and row, 47 in the kernel against 7, and the
+    // launch takes 10.9 us where this form takes 5.7 (2048 graphs of 23 nodes, 104 columns).
+    int r = rows.beg;
+    for (; r + 3 < rows.end; r += 4) {        // four independent row loads per trip, compared in row order
         float v[4][VEC];
 #pragma unroll
         for (int u = 0; u < 4; ++u) ldv<VEC>(p.x + (int64_t)(r + u) * p.xs + c0, v[u]);
 #pragma unroll
         for (int u = 0; u < 4; ++u) take<VEC>(acc, arg, v[u], r + u);
     }
-    for (; r < end; ++r) {
+    for (; r < rows.end; ++r) {
         float v[VEC];
         ldv<VEC>(p.x + (int64_t)r * p.xs + c0, v);
         take<VEC>(acc, arg, v, r);
@@ -75,11 +73,11 @@ __global__ void __launch_bounds__(kBlock) pool_max_fwd_kernel(MaxParams p) {
 }
 
 template <int VEC, int L>
-__global__ void __launch_bounds__(kBlock) pool_max_bwd_kernel(MaxParams p) {
+__global__ void __launch_bounds__(kRowBlock) pool_max_bwd_kernel(MaxParams p) {
     p.N = live_rows(p.N, p.n_dyn);
     const int sg = threadIdx.x / L, sl = threadIdx.x % L, c0 = sl * VEC;
     if (c0 >= p.D) return;
-    for (int64_t n = (int64_t)blockIdx.x * (kBlock / L) + sg; n < p.N; n += (int64_t)gridDim.x * (kBlock / L)) {
+    for (int64_t n = (int64_t)blockIdx.x * (kRowBlock / L) + sg; n < p.N; n += (int64_t)gridDim.x * (kRowBlock / L)) {
         const int64_t g = p.batch[n];
         float v[VEC];
         int a[VEC];
@@ -89,20 +87,6 @@ __global__ void __launch_bounds__(kBlock) pool_max_bwd_kernel(MaxParams p) {
         stv<VEC>(p.gx + n * p.gxs + c0, v);
     }
 }
-
-int shape(int D, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> strides, int* vec, int* lanes) {
-    *vec = row_vec(D, ptrs, strides);
-    if ((D + *vec - 1) / *vec > 256) return fail(KPGNN_ELIMIT, "segment_max: D=%d too wide", D);
-    *lanes = row_lanes(D, *vec);
-    return KPGNN_OK;
-}
-
-#define KP_MAX_LAUNCH(KERNEL, GRID)                                                                          \
-    return dispatch_row_shape<256>(vec, lanes, "segment_max", [&](auto V, auto L) {                          \
-        hipLaunchKernelGGL((KERNEL<V.value, L.value>), dim3(GRID), dim3(kBlock), 0, s, p);                   \
-        KPGNN_LAUNCH_CHECK(#KERNEL);                                                                         \
-        return KPGNN_OK;                                                                                     \
-    })
 
 int check(const kpgnn_pool_max_desc* d, const char* who) {
     KPGNN_REQUIRE(d != nullptr, "%s: NULL descriptor", who);
@@ -121,15 +105,11 @@ extern "C" int kpgnn_segment_max_fwd(const kpgnn_pool_max_desc* d, kpgnn_stream_
     if (d->G == 0) return KPGNN_OK;
     KPGNN_REQUIRE(d->graph_ptr && d->out && (d->N == 0 || (d->x && d->x_stride >= d->D)),
                   "segment_max_fwd: NULL graph_ptr/x/out or bad stride");
-    int vec, lanes;
-    rc = shape(d->D, {d->x, d->out, d->arg}, {d->x_stride}, &vec, &lanes);
-    if (rc != KPGNN_OK) return rc;
     MaxParams p = {};
     p.N = d->N; p.n_dyn = d->n_dyn; p.G = d->G; p.D = d->D; p.ptr = d->graph_ptr; p.x = d->x; p.xs = d->x_stride;
     p.out = d->out; p.arg = d->arg;
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned grid = (unsigned)((d->G + (kBlock / lanes) - 1) / (kBlock / lanes));
-    KP_MAX_LAUNCH(pool_max_fwd_kernel, grid);
+    return launch_row_walk(d->D, {d->x, d->out, d->arg}, {d->x_stride}, "segment_max", "pool_max_fwd_kernel", graph_grid, d->G, p,
+                           (hipStream_t)stream, [](auto V, auto L) { return pool_max_fwd_kernel<V.value, L.value>; });
 }
 
 extern "C" int kpgnn_segment_max_bwd(const kpgnn_pool_max_desc* d, kpgnn_stream_t stream) {
@@ -138,16 +118,9 @@ extern "C" int kpgnn_segment_max_bwd(const kpgnn_pool_max_desc* d, kpgnn_stream_
     if (d->N == 0) return KPGNN_OK;
     KPGNN_REQUIRE(d->G >= 1 && d->batch && d->arg && d->gout && d->gx && d->gx_stride >= d->D,
                   "segment_max_bwd: no graphs, NULL batch/arg/gout/gx or bad stride");
-    int vec, lanes;
-    rc = shape(d->D, {d->gout, d->arg, d->gx}, {d->gx_stride}, &vec, &lanes);
-    if (rc != KPGNN_OK) return rc;
     MaxParams p = {};
     p.N = d->N; p.n_dyn = d->n_dyn; p.G = d->G; p.D = d->D; p.batch = d->batch;
     p.arg = d->arg; p.gout = d->gout; p.gx = d->gx; p.gxs = d->gx_stride;
-    hipStream_t s = (hipStream_t)stream;
-    const int rows = kBlock / lanes;
-    int64_t g = (d->N + rows * 4 - 1) / (rows * 4);
-    const int64_t cap = (int64_t)device_facts().cu_count * 8;
-    const unsigned grid = (unsigned)(g > cap ? cap : (g < 1 ? 1 : g));
-    KP_MAX_LAUNCH(pool_max_bwd_kernel, grid);
+    return launch_row_walk(d->D, {d->gout, d->arg, d->gx}, {d->gx_stride}, "segment_max", "pool_max_bwd_kernel", row_grid, d->N, p,
+                           (hipStream_t)stream, [](auto V, auto L) { return pool_max_bwd_kernel<V.value, L.value>; });
 }

@@ -6,22 +6,17 @@
 // tensor - the dead rows of a capacity-shaped batch included.  Here:
 //   fwd  one streaming launch on the shared row shapes (a group of G lanes owns a row, VEC columns per lane, w and b in
 //        registers), live rows only;
-//   bwd  rd_stats_kernel: every thread sums dy and rd * dy of its columns over its rows in DOUBLE, the block adds its row
-//        groups in group order and writes one partial double[2][H] (zeros included: the workspace need not be cleared);
+//   bwd  rd_stats_kernel: the statistics block of column_stats.h over dy and rd * dy, one partial double[2][H] per block;
 //        rd_finalize_kernel: one block adds the partials in block order and writes dw, db as fp32.
 // Row r belongs to block (r / R) mod kMaxStatGrid whatever the capacity, R the rows of one block pass, and blocks without a
 // live row contribute +0.0: the sums depend on the live rows alone.  dx is dy itself and costs nothing.  No atomics.
-#include "kpgnn_common.h"
+#include "column_stats.h"
 
 namespace kpgnn {
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kRowBlock;
 constexpr int kMaxH = 256;
-constexpr int kMaxStatGrid = 256;    // one block per CU
-constexpr int kFinBlock = 1024;
-constexpr int kMaxSlices = 16;
-constexpr int kMaxApplyGrid = 2048;
 
 struct RdProjParams {
     const int32_t* n_dyn;
@@ -55,56 +50,15 @@ __global__ void __launch_bounds__(kBlock) rd_fwd_kernel(const RdProjParams p) {
 
 template <int VEC, int G>
 __global__ void __launch_bounds__(kBlock) rd_stats_kernel(const RdProjParams p) {
-    constexpr int R = kBlock / G, W = G * VEC;          // rows per pass; columns a pass spans (>= H)
-    __shared__ double sm[2 * kBlock * VEC];             // [2][R][W]
-    const int64_t n = live_rows(p.N, p.n_dyn);
-    const int lane = threadIdx.x % G, rg = threadIdx.x / G, c0 = lane * VEC;
-    double a0[VEC], a1[VEC];
-#pragma unroll
-    for (int q = 0; q < VEC; ++q) a0[q] = a1[q] = 0.0;
-    if (c0 < p.H) {
-        const int64_t step = (int64_t)kMaxStatGrid * R;        // NOT gridDim.x: a row's block does not depend on the capacity
-        int64_t row = (int64_t)blockIdx.x * R + rg;
-        for (; row + 3 * step < n; row += 4 * step) {          // four rows' loads in flight, added in row order
-            float v[4][VEC], r[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                ldv<VEC>(p.dy + (row + u * step) * p.ds + c0, v[u]);
-                r[u] = p.rd[row + u * step];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int q = 0; q < VEC; ++q) {
-                    a0[q] += (double)v[u][q];
-                    a1[q] = fma((double)r[u], (double)v[u][q], a1[q]);
-                }
-        }
-        for (; row < n; row += step) {
-            float v[VEC];
-            ldv<VEC>(p.dy + row * p.ds + c0, v);
-            const double r = (double)p.rd[row];
-#pragma unroll
-            for (int q = 0; q < VEC; ++q) {
-                a0[q] += (double)v[q];
-                a1[q] = fma(r, (double)v[q], a1[q]);
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < VEC; ++q) {
-        sm[(0 * R + rg) * W + c0 + q] = a0[q];
-        sm[(1 * R + rg) * W + c0 + q] = a1[q];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < p.H) {
-        const int c = threadIdx.x;
-        double t0 = 0.0, t1 = 0.0;
-        for (int q = 0; q < R; ++q) { t0 += sm[(0 * R + q) * W + c]; t1 += sm[(1 * R + q) * W + c]; }
-        double* dst = p.part + (int64_t)blockIdx.x * 2 * p.H;
-        dst[c] = t0;
-        dst[p.H + c] = t1;
-    }
+    const int c0 = (int)(threadIdx.x % G) * VEC;
+    // f = dy, m = rd[row] for every column (sum dy, sum rd dy); the step is NOT gridDim.x * R: a row's block does not depend
+    // on the capacity
+    column_stats_block<VEC, G>(live_rows(p.N, p.n_dyn), (int64_t)kMaxStatGrid * (kBlock / G), p.H, p.part,
+                               [&](int64_t row, float (&f)[VEC], float (&m)[VEC]) {
+        ldv<VEC>(p.dy + row * p.ds + c0, f);
+        const float r = p.rd[row];
+        for (int q = 0; q < VEC; ++q) m[q] = r;
+    });
 }
 
 // Slice sl adds the blocks sl, sl + nsl, ... in order, then the slices are added in order; nsl depends on H alone, and only
@@ -131,11 +85,6 @@ __global__ void __launch_bounds__(kFinBlock) rd_finalize_kernel(const RdProjPara
         if (t < p.H) p.db[t] = (float)s;
         else p.dw[t - p.H] = (float)s;
     }
-}
-
-int stat_blocks(int64_t N, int R) {
-    const int64_t b = (N + R - 1) / R;
-    return (int)(b < 1 ? 1 : (b > kMaxStatGrid ? kMaxStatGrid : b));
 }
 
 size_t workspace_bytes(int64_t N, int H) {      // (R >= 1 whatever the row shape turns out to be)

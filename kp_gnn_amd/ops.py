@@ -1377,11 +1377,15 @@ def graph_ptr_of(batch, num_graphs):
     return ptr
 
 
+def _rows_view(t, C):
+    """[N,C] fp32 rows the kernels can walk: unit column stride, rows that do not overlap (a column slice stays a view)."""
+    return t if t.stride(1) == 1 and t.stride(0) >= C else t.contiguous()
+
+
 def _segment_pool_launch(x, ptr, num_graphs, mean=False):
     """[G,D] sum / mean of the rows of x [N,D] per graph: one kpgnn_segment_pool_fwd launch."""
     N, D = x.shape
-    if x.stride(1) != 1 or x.stride(0) < D:
-        x = x.contiguous()
+    x = _rows_view(x, D)
     out = torch.empty((num_graphs, D), dtype=torch.float32, device=x.device)
     d = _lib.PoolDesc()
     d.N, d.G, d.D, d.mode = N, num_graphs, D, 1 if mean else 0
@@ -1433,8 +1437,7 @@ def _segment_max_launch(x, ptr, num_graphs, keep_arg):
     """([G,D] column-wise max of the rows of x [N,D] per graph, int32 [G,D] winning rows or None): one kpgnn_segment_max_fwd
     launch.  A strided x with unit column stride is read in place."""
     N, D = x.shape
-    if x.stride(1) != 1 or x.stride(0) < D:
-        x = x.contiguous()
+    x = _rows_view(x, D)
     out = torch.empty((num_graphs, D), dtype=torch.float32, device=x.device)
     arg = torch.empty((num_graphs, D), dtype=torch.int32, device=x.device) if keep_arg else None
     d = _lib.PoolMaxDesc()
@@ -1491,8 +1494,7 @@ def _vn_launch(x, v, ptr, num_graphs, want_pool, out=None):
     """(x + v[g], sum of that per graph + v or None) as one kpgnn_vn_add_pool launch; x [N,D], v [G,D] (row stride 0 allowed);
     into `out` when given (a contiguous [N,D] fp32 tensor)."""
     N, D = x.shape
-    if x.stride(1) != 1 or x.stride(0) < D:
-        x = x.contiguous()
+    x = _rows_view(x, D)
     if v.stride(1) != 1 or 0 < v.stride(0) < D:
         v = v.contiguous()
     if out is None:
@@ -1626,11 +1628,6 @@ def dropout_mask(shape, p, seed, call, device):
     if N:
         _lib.launch("kpgnn_dropout_mask", mask.device, ctypes.byref(d))
     return mask.view(torch.bool)
-
-
-def _rows_view(t, C):
-    """[N,C] fp32 rows the kernels can walk: unit column stride, rows that do not overlap (a column slice stays a view)."""
-    return t if t.stride(1) == 1 and t.stride(0) >= C else t.contiguous()
 
 
 def _dropout_launch(name, x, residual, cell, p):

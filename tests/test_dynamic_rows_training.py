@@ -325,12 +325,14 @@ def test_jk_concat_projection(CAP, H, S, O, live_of):
 
 
 # --------------------------------------------------------------------------------------------------- dense: segment_pool
-@pytest.mark.parametrize("live", _dense_live(1100))
+@pytest.mark.parametrize("live,ptr_end", [pytest.param(n, e, id=str(n) if e == "live" else f"{n}-{e}")
+                                          for e in ("live", "capacity") for n in _dense_live(1100)])
 @pytest.mark.parametrize("D", [104, 13])
 @pytest.mark.parametrize("mean", [False, True])
-def test_segment_pool(mean, D, live):
-    """pool.hip, forward + backward: graph_ptr ends at the live count (as dataset.StaticBatch attaches it); the dead rows of
-    `batch` repeat a valid graph id."""
+def test_segment_pool(mean, D, live, ptr_end):
+    """pool.hip, forward + backward; the dead rows of `batch` repeat a valid graph id.  graph_ptr ends at the live count (as
+    dataset.StaticBatch attaches it) or at the capacity (what ops.graph_ptr_of makes of this `batch`): the kernels clamp it to
+    the live count themselves, so neither the last graph's sum nor its mean divisor may see a dead row."""
     from kp_gnn_amd import ops
     dev, CAP, G, op = _dev(), 1100, 40, "segment_pool"
     g = torch.Generator().manual_seed(D + live)
@@ -346,12 +348,16 @@ def test_segment_pool(mean, D, live):
     if mean:
         pr = pr / sizes.clamp(min=1).unsqueeze(-1)
     (pr * w.double()).sum().backward()
+    ptr_dev = ptr.to(torch.int32).to(dev)
+    if ptr_end == "capacity":
+        ptr_dev[G] = CAP
+        assert torch.equal(ops.graph_ptr_of(batch.to(dev), G), ptr_dev)
 
     def run(poison):
         xs = x.clone()
         xs[live:] = poison
         xd, bd = xs.to(dev).requires_grad_(True), batch.to(dev)
-        setattr(bd, ops._GPTR, ((bd._version, G), ptr.to(torch.int32).to(dev)))
+        setattr(bd, ops._GPTR, ((bd._version, G), ptr_dev))
         with _dynamic(live, CAP):
             out = ops.segment_pool(xd, bd, G, mean=mean)
             (out * w.to(dev)).sum().backward()
