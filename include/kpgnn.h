@@ -1422,6 +1422,76 @@ size_t kpgnn_rd_proj_workspace_bytes(int64_t N, int32_t H);
 int kpgnn_rd_proj_fwd(const kpgnn_rd_proj_desc* d, kpgnn_stream_t stream);
 int kpgnn_rd_proj_bwd(const kpgnn_rd_proj_desc* d, kpgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The K-hop pre-transform on the device (csrc/khop_transform.hip; data_utils.py:20-241, extract_multi_hop_neighbors).  A
+ * restatement of transform_graph / peripheral_stats of csrc/khop_host.cpp (kpgnn_host.h, kpgnn_khop_plan_*), which is the
+ * specification, quirks Q1 - Q8 of SURVEY.md included: raw graphs in, the collated K-hop tensors of the host plan out, bit
+ * for bit.  Integer only, one workgroup (or wavefront) per graph, two passes over the graphs `graph_ids[0 .. n_ids)`:
+ *   kpgnn_khop_dev_count   adjacency (multiplicity and summed type, LDS integer atomics: COO duplicates add, no dependence on
+ *                          the edge order; self loops stay for the recurrence), walk counts W_1 = mult, W_{k+1} = W_k A,
+ *                          the hop sets (spd: targets not reached at an earlier hop; gd: every positive count), and per node
+ *                          its any-hop mask and K-hop out-degree into `workspace`; status[g] for every graph of the launch.
+ *   kpgnn_khop_dev_fill    the same walk again for the graphs whose status is 0, now writing: the K-hop edge list in
+ *                          (src, dst ascending) order with GLOBAL ids (+ node_ptr[g]) at node_off[i] + rank of dst in the
+ *                          any-hop mask, edge_attr [E,K] (column 0 the summed type of the 1-hop edge or 0, hop k > 0
+ *                          min(count, max_edge_attr_num) + 1, zeros in inactive slots), pe_attr zeros (Q1), batch, and the
+ *                          peripheral statistics per (node, hop) when max_hop_num > 0 and max_edge_type > 0.
+ * Between the two the caller scans the degrees: workspace is int64[2 N] - [0, N) the any-hop mask of each node (one bit per
+ * local target), [N, 2 N) its K-hop out-degree, 0 for every node of a graph whose status is not 0 - and node_off[i] is the
+ * exclusive running sum of the degrees (plus whatever the caller adds for graphs it serves by another route), E_out the
+ * total.  Every write of the fill pass is checked against E_out / N.
+ * status[g] (count pass; outputs of a graph are written only where it is 0):
+ *   KPGNN_KHOP_OK 0          served
+ *   KPGNN_KHOP_TOO_LARGE 1   n > max_nodes of this launch (the cap of any launch is KPGNN_KHOP_MAX_NODES: a row is one 64-bit word)
+ *   KPGNN_KHOP_RANGE 2       a walk count >= 2^31 off the diagonal within K hops (the host's KPGNN_HOST_ERANGE)
+ *   KPGNN_KHOP_ENDPOINT 3    an edge endpoint outside [0, n)
+ *   KPGNN_KHOP_TYPE 4        an edge type below 0, or a summed type above KPGNN_KHOP_MAX_TYPE (the histogram's width)
+ *   KPGNN_KHOP_SHAPE 5       K > 16, max_edge_type > 8 or max_hop_num > 8
+ * Walk counts saturate at 2^32 - 1 where the host saturates at 2^40: min(cap, true count) is what either keeps, every use
+ * is "below 2^31, then exact" or "RANGE", so any cap >= 2^31 gives the same answer.  max_nodes <= KPGNN_KHOP_WAVE_NODES: one
+ * wavefront per graph, four graphs per block, no block barrier; above: one block per graph; dynamic LDS for max_nodes and
+ * K either way (75,280 bytes per graph at n = 64, K = 16).  No global atomics, no float, one workgroup per graph in a fixed
+ * order: bitwise reproducible.  G == 0 or n_ids == 0 return KPGNN_OK without a launch; ids outside [0, G) are skipped; edges
+ * are read from [edge_ptr[g], edge_ptr[g+1]) clipped to [0, E_in).
+ * ---------------------------------------------------------------------------------------------- */
+enum { KPGNN_KHOP_OK = 0, KPGNN_KHOP_TOO_LARGE = 1, KPGNN_KHOP_RANGE = 2, KPGNN_KHOP_ENDPOINT = 3, KPGNN_KHOP_TYPE = 4,
+       KPGNN_KHOP_SHAPE = 5 };
+#define KPGNN_KHOP_MAX_NODES 64
+#define KPGNN_KHOP_WAVE_NODES 32
+#define KPGNN_KHOP_MAX_TYPE 63
+#define KPGNN_KHOP_MAX_K 16
+#define KPGNN_KHOP_MAX_T 8
+#define KPGNN_KHOP_MAX_H 8
+
+typedef struct kpgnn_khop_dev_desc {
+    int32_t G, n_ids;           /* graphs of the call; graphs this launch serves */
+    const int32_t* graph_ids;   /* device [n_ids] */
+    int32_t max_nodes, reserved;/* largest n this launch is sized for, 1 .. KPGNN_KHOP_MAX_NODES; 0 */
+    int64_t N;                  /* nodes of the call, node_ptr[G] */
+    const int64_t* node_ptr;    /* device [G+1] */
+    const int64_t* edge_ptr;    /* device [G+1] */
+    const int64_t* edge_index;  /* device [2,E_in] contiguous: LOCAL ids (0 .. n-1 within each graph), edges grouped by graph */
+    const int64_t* edge_attr;   /* device [E_in] edge types, or NULL = every edge has type 2 */
+    int64_t E_in;               /* input edges of the call (the row length of edge_index), < 2^31 */
+    /* the seven fields of kpgnn_khop_args (kpgnn_host.h) */
+    int32_t K, max_edge_attr_num, max_hop_num, max_edge_type, max_edge_count, max_distance_count, kernel, reserved2;   /* kernel: 0 = spd, 1 = gd; 0 */
+    void* workspace; size_t workspace_bytes;       /* >= kpgnn_khop_dev_workspace_bytes(N), 8-byte aligned; count writes, fill reads */
+    int32_t* status;            /* device [G]; count writes, fill reads */
+    /* fill pass only */
+    const int64_t* node_off;    /* device [N]: first K-hop edge of each node */
+    int64_t E_out;              /* K-hop edges of the call (the row length of out_edge_index) */
+    int64_t* out_edge_index;    /* device [2,E_out] */
+    int64_t* out_edge_attr;     /* device [E_out,K] */
+    int64_t* out_pe_attr;       /* device [N,K-1], or NULL */
+    int64_t* out_pea;           /* device [N,K,max_edge_type,2]; required when max_hop_num > 0 and max_edge_type > 0 */
+    int64_t* out_pca;           /* device [N,K,max_hop_num+1]; likewise */
+    int64_t* out_batch;         /* device [N], or NULL */
+} kpgnn_khop_dev_desc;
+
+size_t kpgnn_khop_dev_workspace_bytes(int64_t N);
+int kpgnn_khop_dev_count(const kpgnn_khop_dev_desc* d, kpgnn_stream_t stream);
+int kpgnn_khop_dev_fill(const kpgnn_khop_dev_desc* d, kpgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -401,6 +401,23 @@ class RdProjDesc(ctypes.Structure):
     ]
 
 
+KHOP_OK, KHOP_TOO_LARGE, KHOP_RANGE, KHOP_ENDPOINT, KHOP_TYPE, KHOP_SHAPE = 0, 1, 2, 3, 4, 5    # include/kpgnn.h KPGNN_KHOP_*
+KHOP_MAX_NODES, KHOP_WAVE_NODES, KHOP_MAX_TYPE = 64, 32, 63             # KPGNN_KHOP_MAX_NODES, _WAVE_NODES, _MAX_TYPE
+KHOP_MAX_K, KHOP_MAX_T, KHOP_MAX_H = 16, 8, 8                           # KPGNN_KHOP_MAX_K, _MAX_T, _MAX_H
+
+
+class KhopDevDesc(ctypes.Structure):
+    _fields_ = [
+        ("G", c_i32), ("n_ids", c_i32), ("graph_ids", c_vp), ("max_nodes", c_i32), ("reserved", c_i32), ("N", c_i64),
+        ("node_ptr", c_vp), ("edge_ptr", c_vp), ("edge_index", c_vp), ("edge_attr", c_vp), ("E_in", c_i64),
+        ("K", c_i32), ("max_edge_attr_num", c_i32), ("max_hop_num", c_i32), ("max_edge_type", c_i32),
+        ("max_edge_count", c_i32), ("max_distance_count", c_i32), ("kernel", c_i32), ("reserved2", c_i32),
+        ("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t), ("status", c_vp),
+        ("node_off", c_vp), ("E_out", c_i64), ("out_edge_index", c_vp), ("out_edge_attr", c_vp), ("out_pe_attr", c_vp),
+        ("out_pea", c_vp), ("out_pca", c_vp), ("out_batch", c_vp),
+    ]
+
+
 class AttnPoolDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i64), ("G", c_i32), ("D", c_i32),
@@ -512,6 +529,9 @@ SIGNATURES = {
     "kpgnn_rd_proj_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i32]),
     "kpgnn_rd_proj_fwd": (ctypes.c_int, [ctypes.POINTER(RdProjDesc), c_vp]),
     "kpgnn_rd_proj_bwd": (ctypes.c_int, [ctypes.POINTER(RdProjDesc), c_vp]),
+    "kpgnn_khop_dev_workspace_bytes": (ctypes.c_size_t, [c_i64]),
+    "kpgnn_khop_dev_count": (ctypes.c_int, [ctypes.POINTER(KhopDevDesc), c_vp]),
+    "kpgnn_khop_dev_fill": (ctypes.c_int, [ctypes.POINTER(KhopDevDesc), c_vp]),
     "kpgnn_vn_add_pool": (ctypes.c_int, [ctypes.POINTER(VnDesc), c_vp]),
     "kpgnn_dropout_fwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
     "kpgnn_dropout_bwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),

@@ -92,88 +92,158 @@ class KHopDataset:
             edge_ptr = np.concatenate([[0], np.cumsum(edge_cnt)])
         edge_ptr = np.asarray(edge_ptr, dtype=np.int64)
         edge_cnt = np.diff(edge_ptr)
-        parts = {k: [] for k in ("rowptr_dst", "rowptr_src", "col_dst", "col_src", "code_dst", "code_src", "ent_rel", "ent")}
-        pair_cnt, ent_cnt, hop_cnt = [], [], []
-        max0 = maxk = 0
         dev = ds.device
         given_rd = getattr(batch, "rd", None)
-        rd_parts = [] if (with_rd and given_rd is None) else None
+        acc = ds._begin(with_entry_lists, with_rd and given_rd is None)
         for g0 in range(0, G, chunk_graphs):
             g1 = min(G, g0 + chunk_graphs)
-            n0, n1, e0, e1 = int(node_ptr[g0]), int(node_ptr[g1]), int(edge_ptr[g0]), int(edge_ptr[g1])
-            Nc = n1 - n0
+            n0, e0, e1 = int(node_ptr[g0]), int(edge_ptr[g0]), int(edge_ptr[g1])
             cei = (ei[:, e0:e1] - n0).to(dev)
             cea = ea[e0:e1].to(dev)
-            if rd_parts is not None:
-                from .ops import resistance_distance
-                rd_parts.append(resistance_distance(node_ptr[g0:g1 + 1] - n0, edge_ptr[g0:g1 + 1] - e0, cei, dev)[0])
-            csr = KHopCSR.build(cei, cea, Nc, nodes_per_tile=1 if with_entry_lists else None)
-            max0, maxk = max(max0, csr.max_code0), max(maxk, csr.max_codek)
-            nptr = torch.from_numpy(node_ptr[g0:g1 + 1] - n0).to(dev)                 # [gc+1] chunk-local node offsets
-            gnodes = nptr[1:] - nptr[:-1]
-            graph_of_node = torch.repeat_interleave(torch.arange(g1 - g0, device=dev), gnodes)
-            pptr = csr.rowptr_dst[(nptr * K).long()].long()                           # [gc+1] first pair of each graph
-            assert torch.equal(pptr, csr.rowptr_src[(nptr * K).long()].long()), "orientations disagree on a graph's pair count"
-            seg_graph = graph_of_node.repeat_interleave(K)
-            parts["rowptr_dst"].append((csr.rowptr_dst[:-1].long() - pptr[seg_graph]).to(torch.int32))
-            parts["rowptr_src"].append((csr.rowptr_src[:-1].long() - pptr[seg_graph]).to(torch.int32))
-            if csr.A:
-                graph_of_pair = torch.bucketize(torch.arange(csr.A, device=dev), pptr[1:], right=True)
-                nb = nptr[graph_of_pair].to(torch.int32)
-                parts["col_dst"].append(csr.col_dst[:csr.A] - nb)
-                parts["col_src"].append(csr.col_src[:csr.A] - nb)
-                parts["code_dst"].append(csr.code_dst[:csr.A].clone())
-                parts["code_src"].append(csr.code_src[:csr.A].clone())
-            pair_cnt.append((pptr[1:] - pptr[:-1]).cpu().numpy())
-            # active pairs per graph within the first k hops (byte accounting of layers that see a hop prefix)
-            seg_len = (csr.rowptr_dst[1:] - csr.rowptr_dst[:-1]).view(Nc, K).long()
-            per_graph = torch.zeros((g1 - g0, K), dtype=torch.long, device=dev).index_add_(0, graph_of_node, seg_len)
-            hop_cnt.append(per_graph.cumsum(1).cpu().numpy())
-            if with_entry_lists:
-                eptr = csr.tile_ptr[nptr.long()].long()                               # nodes_per_tile = 1: tile == node
-                parts["ent_rel"].append((csr.tile_ptr[:-1].long() - eptr[graph_of_node]).to(torch.int32))
-                n_e = int(eptr[-1].item())
-                parts["ent"].append(csr.tile_pack[:n_e].clone())
-                ent_cnt.append((eptr[1:] - eptr[:-1]).cpu().numpy())
-            del csr, cei, cea
-        cat = lambda k, dt: (torch.cat(parts[k]) if parts[k] else torch.zeros(0, dtype=dt, device=dev))  # noqa: E731
-        ds.rowptr_dst, ds.rowptr_src = cat("rowptr_dst", torch.int32), cat("rowptr_src", torch.int32)
-        ds.col_dst, ds.col_src = cat("col_dst", torch.int32), cat("col_src", torch.int32)
-        ds.code_dst, ds.code_src = cat("code_dst", torch.int16), cat("code_src", torch.int16)
-        ds.has_entries = with_entry_lists
-        ds.max_mult = 0
-        if with_entry_lists:
-            ds.ent_rel, ds.ent = cat("ent_rel", torch.int32), cat("ent", torch.int32)
-            ds.max_mult = int(((ds.ent >> 6) & 63).max().item()) + 1 if ds.ent.numel() else 1     # largest entry multiplicity
-        ds.max_code0, ds.max_codek = max0, maxk
-        # per-graph counts (host) and their running sums (device, int64)
-        ds.h_nodes = np.diff(node_ptr)
-        ds.h_pairs = np.concatenate(pair_cnt) if pair_cnt else np.zeros(0, np.int64)
-        ds.h_ents = np.concatenate(ent_cnt) if ent_cnt else np.zeros(G, np.int64)
-        ds.h_edges = edge_cnt
-        ds.h_hop_pairs = np.concatenate(hop_cnt) if hop_cnt else np.zeros((0, K), np.int64)
-        run = lambda c: torch.from_numpy(np.concatenate([[0], np.cumsum(c)]).astype(np.int64)).to(dev)  # noqa: E731
-        ds.node_ptr, ds.pair_ptr, ds.ent_ptr = run(ds.h_nodes), run(ds.h_pairs), run(ds.h_ents)
-        # node / graph attributes
-        x = batch.x
-        if x is not None:
-            if not x.is_floating_point():
-                ds._add_index_rows("x", x)
-            else:
-                ds.node_rows["x"] = x.to(dev).contiguous()
-        if getattr(batch, "z", None) is not None:
-            ds._add_index_rows("z", batch.z)
-        if given_rd is not None:
-            ds.node_rows["rd"] = given_rd.to(device=dev, dtype=torch.float32).reshape(Nd, 1).contiguous()
-        elif rd_parts is not None:
-            ds.node_rows["rd"] = torch.cat(rd_parts) if rd_parts else torch.zeros((0, 1), dtype=torch.float32, device=dev)
-        if batch.y is not None:
-            ds.graph_rows["y"] = batch.y.to(dev).contiguous()
+            ds._add_chunk(acc, cei, cea, node_ptr[g0:g1 + 1] - n0, edge_ptr[g0:g1 + 1] - e0)
+            del cei, cea
+        ds._finish(acc, node_ptr, edge_cnt)
+        ds._attach_rows(batch.x, getattr(batch, "z", None), batch.y, given_rd)
         pea, pca = batch.peripheral_edge_attr, batch.peripheral_configuration_attr
         if pea is not None and pca is not None:
             ds._build_dictionary(pea, pca)
-        ds.Nd = Nd
         return ds
+
+    @staticmethod
+    def from_graphs(node_ptr, edge_ptr, edge_index, edge_attr, device, khop_args, x=None, z=None, y=None, chunk_graphs=4096,
+                    with_entry_lists=True, with_rd=False, route="auto"):
+        """The dataset from RAW graphs: node_ptr / edge_ptr [G+1] host offsets, edge_index [2,E] LOCAL ids and edge_attr [E] or
+        None (what khop_transform.khop_batch takes), khop_args = (K, max_edge_attr_num, max_hop_num, max_edge_type,
+        max_edge_count, max_distance_count, kernel); x / z [N, ...] node and y [G, ...] graph attributes.
+        route "device": per chunk ops.khop_transform (the K-hop tensors are made on the device and never exist on the host; a
+        graph its kernel does not serve takes the host route inside that call), then KHopCSR.build on the tensors where they
+        lie, then the rd column if asked; the dictionary comes from the device peripheral tensors.  route "host":
+        khop_batch + from_collated.  "auto" is the device route: DESIGN.md 5.20 has the measurement behind it.  Either route
+        gives the same dataset, bit for bit."""
+        if route not in ("auto", "device", "host"):
+            raise ValueError(f"unknown route {route!r}")
+        from . import khop_transform as KT
+        node_ptr, edge_ptr = np.asarray(node_ptr, dtype=np.int64), np.asarray(edge_ptr, dtype=np.int64)
+        as_t = lambda a: a if a is None or torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
+        edge_index, edge_attr, x, z, y = as_t(edge_index), as_t(edge_attr), as_t(x), as_t(z), as_t(y)
+        if route == "host":
+            from .batch import KHopBatch
+            out = KT.khop_batch(node_ptr, edge_ptr, edge_index.cpu().numpy(), None if edge_attr is None else edge_attr.cpu().numpy(),
+                                *khop_args)
+            hb = KHopBatch(x=x, z=z, y=y, edge_index=out["edge_index"], edge_attr=out["edge_attr"], pe_attr=out["pe_attr"],
+                           peripheral_edge_attr=out["peripheral_edge_attr"],
+                           peripheral_configuration_attr=out["peripheral_configuration_attr"], batch=out["batch"],
+                           num_graphs=node_ptr.shape[0] - 1)
+            hb.edge_ptr = out["edge_ptr"].numpy()
+            return KHopDataset.from_collated(hb, node_ptr, device, chunk_graphs, with_entry_lists, with_rd)
+        from .ops import khop_transform
+        ds = KHopDataset()
+        G = node_ptr.shape[0] - 1
+        ds.G, ds.K, ds.device = G, int(khop_args[0]), torch.device(device)
+        acc = ds._begin(with_entry_lists, with_rd)
+        edge_cnt, peas, pcas = [], [], []
+        for g0 in range(0, G, chunk_graphs):
+            g1 = min(G, g0 + chunk_graphs)
+            n0, e0, e1 = int(node_ptr[g0]), int(edge_ptr[g0]), int(edge_ptr[g1])
+            out, _ = khop_transform(node_ptr[g0:g1 + 1] - n0, edge_ptr[g0:g1 + 1] - e0, edge_index[:, e0:e1],
+                                    None if edge_attr is None else edge_attr[e0:e1], *khop_args, ds.device)
+            k_eptr = out["edge_ptr"].cpu().numpy()
+            edge_cnt.append(np.diff(k_eptr))
+            ds._add_chunk(acc, out["edge_index"], out["edge_attr"], node_ptr[g0:g1 + 1] - n0, k_eptr)
+            if out["peripheral_edge_attr"] is not None:
+                peas.append(out["peripheral_edge_attr"])
+                pcas.append(out["peripheral_configuration_attr"])
+            del out
+        ds._finish(acc, node_ptr, np.concatenate(edge_cnt) if edge_cnt else np.zeros(0, np.int64))
+        ds._attach_rows(x, z, y, None)
+        if peas:
+            ds._build_dictionary(torch.cat(peas), torch.cat(pcas))
+        return ds
+
+    def _begin(self, with_entry_lists, with_rd):
+        """What the chunks of a construction add up to (_add_chunk) before _finish joins them; with_rd: every chunk also
+        computes the resistance-distance column from its K-hop edge list."""
+        return {"parts": {k: [] for k in ("rowptr_dst", "rowptr_src", "col_dst", "col_src", "code_dst", "code_src", "ent_rel", "ent")},
+                "pair_cnt": [], "ent_cnt": [], "hop_cnt": [], "max0": 0, "maxk": 0, "rd": [] if with_rd else None, "entries": with_entry_lists}
+
+    def _add_chunk(self, acc, cei, cea, nptr_h, eptr_h):
+        """One chunk of graphs: cei [2,Ec] / cea [Ec,K] its K-hop edge list ON THE DEVICE with chunk-local node ids, nptr_h /
+        eptr_h [gc+1] its chunk-local node and K-hop edge offsets (host).  Builds the chunk's CSR, makes it graph-local and
+        keeps the per-graph counts."""
+        dev, K, parts, with_entry_lists = self.device, self.K, acc["parts"], acc["entries"]
+        gc, Nc = nptr_h.shape[0] - 1, int(nptr_h[-1])
+        if acc["rd"] is not None:
+            from .ops import resistance_distance
+            acc["rd"].append(resistance_distance(nptr_h, eptr_h, cei, dev)[0])
+        csr = KHopCSR.build(cei, cea, Nc, nodes_per_tile=1 if with_entry_lists else None)
+        acc["max0"], acc["maxk"] = max(acc["max0"], csr.max_code0), max(acc["maxk"], csr.max_codek)
+        nptr = torch.from_numpy(np.ascontiguousarray(nptr_h)).to(dev)             # [gc+1] chunk-local node offsets
+        gnodes = nptr[1:] - nptr[:-1]
+        graph_of_node = torch.repeat_interleave(torch.arange(gc, device=dev), gnodes)
+        pptr = csr.rowptr_dst[(nptr * K).long()].long()                           # [gc+1] first pair of each graph
+        assert torch.equal(pptr, csr.rowptr_src[(nptr * K).long()].long()), "orientations disagree on a graph's pair count"
+        seg_graph = graph_of_node.repeat_interleave(K)
+        parts["rowptr_dst"].append((csr.rowptr_dst[:-1].long() - pptr[seg_graph]).to(torch.int32))
+        parts["rowptr_src"].append((csr.rowptr_src[:-1].long() - pptr[seg_graph]).to(torch.int32))
+        if csr.A:
+            graph_of_pair = torch.bucketize(torch.arange(csr.A, device=dev), pptr[1:], right=True)
+            nb = nptr[graph_of_pair].to(torch.int32)
+            parts["col_dst"].append(csr.col_dst[:csr.A] - nb)
+            parts["col_src"].append(csr.col_src[:csr.A] - nb)
+            parts["code_dst"].append(csr.code_dst[:csr.A].clone())
+            parts["code_src"].append(csr.code_src[:csr.A].clone())
+        acc["pair_cnt"].append((pptr[1:] - pptr[:-1]).cpu().numpy())
+        # active pairs per graph within the first k hops (byte accounting of layers that see a hop prefix)
+        seg_len = (csr.rowptr_dst[1:] - csr.rowptr_dst[:-1]).view(Nc, K).long()
+        per_graph = torch.zeros((gc, K), dtype=torch.long, device=dev).index_add_(0, graph_of_node, seg_len)
+        acc["hop_cnt"].append(per_graph.cumsum(1).cpu().numpy())
+        if with_entry_lists:
+            eptr = csr.tile_ptr[nptr.long()].long()                               # nodes_per_tile = 1: tile == node
+            parts["ent_rel"].append((csr.tile_ptr[:-1].long() - eptr[graph_of_node]).to(torch.int32))
+            n_e = int(eptr[-1].item())
+            parts["ent"].append(csr.tile_pack[:n_e].clone())
+            acc["ent_cnt"].append((eptr[1:] - eptr[:-1]).cpu().numpy())
+
+    def _finish(self, acc, node_ptr, edge_cnt):
+        """Join the chunks: the graph-local CSR arrays, the per-graph counts (host) and their running sums (device, int64)."""
+        dev, G, K, parts, with_entry_lists = self.device, self.G, self.K, acc["parts"], acc["entries"]
+        cat = lambda k, dt: (torch.cat(parts[k]) if parts[k] else torch.zeros(0, dtype=dt, device=dev))  # noqa: E731
+        self.rowptr_dst, self.rowptr_src = cat("rowptr_dst", torch.int32), cat("rowptr_src", torch.int32)
+        self.col_dst, self.col_src = cat("col_dst", torch.int32), cat("col_src", torch.int32)
+        self.code_dst, self.code_src = cat("code_dst", torch.int16), cat("code_src", torch.int16)
+        self.has_entries = with_entry_lists
+        self.max_mult = 0
+        if with_entry_lists:
+            self.ent_rel, self.ent = cat("ent_rel", torch.int32), cat("ent", torch.int32)
+            self.max_mult = int(((self.ent >> 6) & 63).max().item()) + 1 if self.ent.numel() else 1     # largest entry multiplicity
+        self.max_code0, self.max_codek = acc["max0"], acc["maxk"]
+        self.h_nodes = np.diff(node_ptr)
+        self.h_pairs = np.concatenate(acc["pair_cnt"]) if acc["pair_cnt"] else np.zeros(0, np.int64)
+        self.h_ents = np.concatenate(acc["ent_cnt"]) if acc["ent_cnt"] else np.zeros(G, np.int64)
+        self.h_edges = edge_cnt
+        self.h_hop_pairs = np.concatenate(acc["hop_cnt"]) if acc["hop_cnt"] else np.zeros((0, K), np.int64)
+        run = lambda c: torch.from_numpy(np.concatenate([[0], np.cumsum(c)]).astype(np.int64)).to(dev)  # noqa: E731
+        self.node_ptr, self.pair_ptr, self.ent_ptr = run(self.h_nodes), run(self.h_pairs), run(self.h_ents)
+        self.Nd = int(node_ptr[-1])
+        self._rd_parts = acc["rd"]
+
+    def _attach_rows(self, x, z, y, given_rd):
+        """Node / graph attributes; `given_rd` wins over the column _add_chunk computed."""
+        dev = self.device
+        rd_parts, self._rd_parts = self._rd_parts, None
+        if x is not None:
+            if not x.is_floating_point():
+                self._add_index_rows("x", x)
+            else:
+                self.node_rows["x"] = x.to(dev).contiguous()
+        if z is not None:
+            self._add_index_rows("z", z)
+        if given_rd is not None:
+            self.node_rows["rd"] = given_rd.to(device=dev, dtype=torch.float32).reshape(self.Nd, 1).contiguous()
+        elif rd_parts is not None:
+            self.node_rows["rd"] = torch.cat(rd_parts) if rd_parts else torch.zeros((0, 1), dtype=torch.float32, device=dev)
+        if y is not None:
+            self.graph_rows["y"] = y.to(dev).contiguous()
 
     def _add_index_rows(self, name, t):
         lo, hi = int(t.min()), int(t.max())

@@ -119,17 +119,24 @@ def khop_batch(node_ptr, edge_ptr, edge_index, edge_attr, K, max_edge_attr_num, 
 def extract_multi_hop_neighbors(data, K, max_edge_attr_num, max_hop_num, max_edge_type, max_edge_count,
                                 max_distance_count, kernel):
     """Same contract as the reference's data_utils.extract_multi_hop_neighbors (:20-107): rewrites and
-    returns `data` (any object with x / edge_index / optional edge_attr / num_nodes attributes)."""
+    returns `data` (any object with x / edge_index / optional edge_attr / num_nodes attributes).  A device `edge_index` takes
+    the batched kernel (ops.khop_transform, one graph) and the results stay on that device; a host one the OpenMP library."""
     edge_index = data.edge_index
     num_nodes = data.num_nodes if getattr(data, "num_nodes", None) is not None else data.x.size(0)
     if edge_index.size(1) == 0:  # reference :36-44 (note the different attribute name and width, Q8)
-        data.peripheral_edge_attr = torch.zeros([num_nodes, K, max_edge_type, 2], dtype=torch.long)
-        data.peripheral_configuration = torch.zeros([num_nodes, K, max_hop_num], dtype=torch.long)
+        where = edge_index.device
+        data.peripheral_edge_attr = torch.zeros([num_nodes, K, max_edge_type, 2], dtype=torch.long, device=where)
+        data.peripheral_configuration = torch.zeros([num_nodes, K, max_hop_num], dtype=torch.long, device=where)
         return data
     ea = getattr(data, "edge_attr", None)
-    out = khop_batch([0, num_nodes], [0, edge_index.size(1)], edge_index.cpu().numpy(),
-                     None if ea is None else ea.cpu().numpy(), K, max_edge_attr_num, max_hop_num, max_edge_type,
-                     max_edge_count, max_distance_count, kernel, num_threads=1)
+    if edge_index.is_cuda:      # the device route (ops.khop_transform, one graph); the results stay where edge_index lives
+        from .ops import khop_transform as khop_device
+        out = khop_device([0, num_nodes], [0, edge_index.size(1)], edge_index, ea, K, max_edge_attr_num, max_hop_num,
+                          max_edge_type, max_edge_count, max_distance_count, kernel, edge_index.device)[0]
+    else:
+        out = khop_batch([0, num_nodes], [0, edge_index.size(1)], edge_index.cpu().numpy(),
+                         None if ea is None else ea.cpu().numpy(), K, max_edge_attr_num, max_hop_num, max_edge_type,
+                         max_edge_count, max_distance_count, kernel, num_threads=1)
     data.edge_index = out["edge_index"]
     data.edge_attr = out["edge_attr"]
     data.peripheral_edge_attr = out["peripheral_edge_attr"]

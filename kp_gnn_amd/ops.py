@@ -2206,6 +2206,126 @@ def resistance_distance(node_ptr, edge_ptr, edge_index, device):
     return out, status
 
 
+# ------------------------------------------------------------------------------------------------ the K-hop pre-transform
+def khop_transform(node_ptr, edge_ptr, edge_index, edge_attr, K, max_edge_attr_num, max_hop_num, max_edge_type,
+                   max_edge_count, max_distance_count, kernel, device):
+    """khop_transform.khop_batch on the device: (the same dict of collated int64 tensors, on `device`; status [G] int32 on the
+    host).  node_ptr / edge_ptr [G+1]: host offsets; edge_index [2,E] LOCAL ids and edge_attr [E] or None, host or device.
+    The graphs are bucketed by size (n <= 32: a wavefront per graph; n <= 64: a block per graph), kpgnn_khop_dev_count runs per
+    class, the per-graph edge counts and `status` come back in ONE read, the degrees are scanned with cumsum, and
+    kpgnn_khop_dev_fill writes the tensors.  Graphs the kernel did not serve - more than 64 nodes (1), a summed edge type above
+    63 (4), K / max_edge_type / max_hop_num beyond 16 / 8 / 8 (5) - go through khop_batch on the host: their edge counts join
+    the scan and their slices are copied in, so the result is the same whichever route served a graph.  A walk count >= 2^31
+    (2) raises what khop_batch raises for that graph (KpgnnError), an edge endpoint outside its graph (3) ValueError."""
+    from . import khop_transform as KT
+    node_ptr, edge_ptr = _host_i64(node_ptr), _host_i64(edge_ptr)
+    G = node_ptr.shape[0] - 1
+    if G < 0 or edge_ptr.shape[0] != G + 1:
+        raise ValueError("node_ptr and edge_ptr must both have G + 1 entries")
+    if node_ptr[0] != 0 or edge_ptr[0] != 0 or bool((np.diff(node_ptr) < 0).any()) or bool((np.diff(edge_ptr) < 0).any()):
+        raise ValueError("node_ptr / edge_ptr must start at 0 and not decrease")
+    N, E = int(node_ptr[-1]), int(edge_ptr[-1])
+    if not torch.is_tensor(edge_index):
+        edge_index = torch.from_numpy(np.ascontiguousarray(np.asarray(edge_index, dtype=np.int64)))
+    edge_index = edge_index.reshape(2, -1)
+    if edge_index.shape[1] != E:
+        raise ValueError("edge_index does not match edge_ptr")
+    if edge_attr is not None:
+        if not torch.is_tensor(edge_attr):
+            edge_attr = torch.from_numpy(np.ascontiguousarray(np.asarray(edge_attr, dtype=np.int64)))
+        edge_attr = edge_attr.reshape(-1)
+        if edge_attr.shape[0] != E:
+            raise ValueError("edge_attr does not match edge_ptr")
+    if kernel not in ("spd", "gd"):
+        raise ValueError(f"unknown kernel {kernel!r}")
+    if K < 1 or min(max_edge_attr_num, max_hop_num, max_edge_type, max_edge_count, max_distance_count) < 0:
+        raise ValueError("bad K-hop arguments")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.KpgnnError("ops.khop_transform is the device route: khop_transform.khop_batch is the host one")
+    args = (K, max_edge_attr_num, max_hop_num, max_edge_type, max_edge_count, max_distance_count, kernel)
+    want_p = max_hop_num > 0 and max_edge_type > 0
+    i64 = dict(dtype=torch.int64, device=dev)
+    ei = edge_index.to(**i64).contiguous()
+    ea = None if edge_attr is None else edge_attr.to(**i64).contiguous()
+    nptr, eptr = torch.from_numpy(node_ptr).to(dev), torch.from_numpy(edge_ptr).to(dev)
+    st = torch.zeros(G, dtype=torch.int32, device=dev)
+    ws = torch.zeros(max(2 * N, 1), **i64)                  # [0, N) any-hop masks, [N, 2N) K-hop out-degrees
+    nodes = np.diff(node_ptr)
+    d = _lib.KhopDevDesc()
+    d.G, d.N, d.E_in = G, N, E
+    d.node_ptr, d.edge_ptr, d.edge_index = nptr.data_ptr(), eptr.data_ptr(), ei.data_ptr()
+    d.edge_attr = None if ea is None else ea.data_ptr()
+    d.K, d.max_edge_attr_num, d.max_hop_num, d.max_edge_type, d.max_edge_count, d.max_distance_count = args[:6]
+    d.kernel = 0 if kernel == "spd" else 1
+    d.workspace, d.workspace_bytes, d.status = ws.data_ptr(), ws.numel() * 8, st.data_ptr()
+    classes = []
+    for ids in (np.flatnonzero(nodes <= _lib.KHOP_WAVE_NODES), np.flatnonzero(nodes > _lib.KHOP_WAVE_NODES)):
+        if ids.size:
+            classes.append((torch.from_numpy(ids.astype(np.int32)).to(dev), ids.size,
+                            max(1, min(_lib.KHOP_MAX_NODES, int(nodes[ids].max())))))     # (larger graphs get status 1)
+
+    def run(name):
+        for ids_d, n_ids, cap in classes:
+            d.graph_ids, d.n_ids, d.max_nodes = ids_d.data_ptr(), n_ids, cap
+            _lib.launch(name, dev, ctypes.byref(d), timed=("khop_dev", lambda: 0))
+
+    run("kpgnn_khop_dev_count")
+    deg = ws[N:2 * N]
+    run_sum = torch.cat([deg.new_zeros(1), deg.cumsum(0)])
+    back = torch.cat([st.long(), run_sum[nptr[1:]] - run_sum[nptr[:-1]]]).cpu().numpy()         # the one read
+    status, g_edges = back[:G].astype(np.int32), back[G:].copy()
+    for code in (_lib.KHOP_ENDPOINT, _lib.KHOP_RANGE):
+        hit = np.flatnonzero(status == code)
+        if hit.size:
+            g = int(hit[0])
+            if code == _lib.KHOP_ENDPOINT:
+                raise ValueError(f"graph {g}: an edge endpoint lies outside its {int(nodes[g])} nodes")
+            sl = slice(int(edge_ptr[g]), int(edge_ptr[g + 1]))
+            KT.khop_batch([0, int(nodes[g])], [0, sl.stop - sl.start], edge_index[:, sl].cpu().numpy(),
+                          None if edge_attr is None else edge_attr[sl].cpu().numpy(), *args, num_threads=1)     # raises
+            raise _lib.KpgnnError(f"graph {g}: a walk count >= 2^31 within {K} hops")
+    todo = np.flatnonzero(status != 0)
+    host = None
+    if todo.size:                                           # the host route for what the kernel did not serve
+        ei_h = edge_index.cpu().numpy()
+        ea_h = None if edge_attr is None else edge_attr.cpu().numpy()
+        esl = [np.arange(edge_ptr[g], edge_ptr[g + 1]) for g in todo]
+        ecat = np.concatenate(esl)
+        h_nptr = np.concatenate([[0], np.cumsum(nodes[todo])])
+        h_eptr = np.concatenate([[0], np.cumsum([a.size for a in esl])])
+        host = KT.khop_batch(h_nptr, h_eptr, ei_h[:, ecat], None if ea_h is None else ea_h[ecat], *args)
+        g_edges[todo] = np.diff(host["edge_ptr"].numpy())
+        deg[torch.from_numpy(node_ptr[todo]).to(dev)] = torch.from_numpy(g_edges[todo]).to(dev)   # on the graph's first node
+    out_eptr = np.concatenate([[0], np.cumsum(g_edges)]).astype(np.int64)
+    E_out = int(out_eptr[-1])
+    node_off = deg.cumsum(0) - deg
+    out = {"edge_index": torch.empty((2, E_out), **i64), "edge_attr": torch.empty((E_out, K), **i64),
+           "pe_attr": torch.zeros((N, K - 1), **i64) if K > 1 else None,
+           "peripheral_edge_attr": torch.zeros((N, K, max_edge_type, 2), **i64) if want_p else None,
+           "peripheral_configuration_attr": torch.zeros((N, K, max_hop_num + 1), **i64) if want_p else None,
+           "batch": torch.empty(N, **i64), "edge_ptr": torch.from_numpy(out_eptr).to(dev), "node_ptr": nptr}
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    d.node_off, d.E_out = ptr(node_off), E_out
+    d.out_edge_index, d.out_edge_attr, d.out_pe_attr = ptr(out["edge_index"]), ptr(out["edge_attr"]), ptr(out["pe_attr"])
+    d.out_pea, d.out_pca = ptr(out["peripheral_edge_attr"]), ptr(out["peripheral_configuration_attr"])
+    d.out_batch = ptr(out["batch"])
+    run("kpgnn_khop_dev_fill")
+    if host is not None:
+        h_off = host["edge_ptr"].numpy()
+        e_dst = np.concatenate([np.arange(out_eptr[g], out_eptr[g + 1]) for g in todo])
+        n_dst = np.concatenate([np.arange(node_ptr[g], node_ptr[g + 1]) for g in todo])
+        shift = np.repeat(node_ptr[todo] - h_nptr[:-1], np.diff(h_off))            # host ids -> ids of this call
+        e_dst, n_dst = torch.from_numpy(e_dst).to(dev), torch.from_numpy(n_dst).to(dev)
+        out["edge_index"][:, e_dst] = (host["edge_index"] + torch.from_numpy(shift)).to(dev)
+        out["edge_attr"][e_dst] = host["edge_attr"].to(dev)
+        out["batch"][n_dst] = torch.from_numpy(np.repeat(todo, nodes[todo])).to(dev)
+        for k in ("pe_attr", "peripheral_edge_attr", "peripheral_configuration_attr"):
+            if out[k] is not None:
+                out[k][n_dst] = host[k].to(dev)
+    return out, torch.from_numpy(status)
+
+
 # ------------------------------------------------------------------------------------------------ the rd projection
 # x + rd_projection(rd) of the bodies (models/GNNs.py; kpgnn.h, kpgnn_rd_proj_desc): one launch forward; backward dx is the
 # incoming gradient and dw / db are two launches of double partial sums over the LIVE rows - the framework's Linear(1, H)
