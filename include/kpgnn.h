@@ -1466,7 +1466,8 @@ enum { KPGNN_KHOP_OK = 0, KPGNN_KHOP_TOO_LARGE = 1, KPGNN_KHOP_RANGE = 2, KPGNN_
 typedef struct kpgnn_khop_dev_desc {
     int32_t G, n_ids;           /* graphs of the call; graphs this launch serves */
     const int32_t* graph_ids;   /* device [n_ids] */
-    int32_t max_nodes, reserved;/* largest n this launch is sized for, 1 .. KPGNN_KHOP_MAX_NODES; 0 */
+    int32_t max_nodes, reserved;/* largest n this launch is sized for, 1 .. KPGNN_KHOP_MAX_NODES (kpgnn_khop_large_*: 1 ..
+                                   KPGNN_KHOP_LARGE_MAX_NODES); 0 */
     int64_t N;                  /* nodes of the call, node_ptr[G] */
     const int64_t* node_ptr;    /* device [G+1] */
     const int64_t* edge_ptr;    /* device [G+1] */
@@ -1475,7 +1476,9 @@ typedef struct kpgnn_khop_dev_desc {
     int64_t E_in;               /* input edges of the call (the row length of edge_index), < 2^31 */
     /* the seven fields of kpgnn_khop_args (kpgnn_host.h) */
     int32_t K, max_edge_attr_num, max_hop_num, max_edge_type, max_edge_count, max_distance_count, kernel, reserved2;   /* kernel: 0 = spd, 1 = gd; 0 */
-    void* workspace; size_t workspace_bytes;       /* >= kpgnn_khop_dev_workspace_bytes(N), 8-byte aligned; count writes, fill reads */
+    void* workspace; size_t workspace_bytes;       /* >= kpgnn_khop_dev_workspace_bytes(N) (kpgnn_khop_large_*: >=
+                                                      kpgnn_khop_large_workspace_bytes(N, E_in, max_nodes)), 8-byte aligned;
+                                                      count writes, fill reads */
     int32_t* status;            /* device [G]; count writes, fill reads */
     /* fill pass only */
     const int64_t* node_off;    /* device [N]: first K-hop edge of each node */
@@ -1491,6 +1494,43 @@ typedef struct kpgnn_khop_dev_desc {
 size_t kpgnn_khop_dev_workspace_bytes(int64_t N);
 int kpgnn_khop_dev_count(const kpgnn_khop_dev_desc* d, kpgnn_stream_t stream);
 int kpgnn_khop_dev_fill(const kpgnn_khop_dev_desc* d, kpgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The same pre-transform for graphs above KPGNN_KHOP_MAX_NODES nodes (csrc/khop_large.hip): the same descriptor (layout
+ * unchanged, reserved fields 0), the same input contract (raw COO with local ids, grouped by graph, any order within a graph;
+ * duplicates add; self loops stay for the recurrence; directed lists allowed), the same status codes where the pair above
+ * reports them (TOO_LARGE: n > max_nodes of THIS launch), the same K / max_edge_type / max_hop_num limits 16 / 8 / 8 and
+ * summed-type limit 63, and bit for bit the tensors of the host route for a graph of 1 .. KPGNN_KHOP_LARGE_MAX_NODES nodes -
+ * one of 64 nodes or fewer included.  max_nodes above KPGNN_KHOP_LARGE_MAX_NODES answers KPGNN_ELIMIT.
+ * The unit of work is a SOURCE NODE (row i of W_k depends only on row i of W_{k-1}): one wavefront walks one row with two
+ * uint32 count rows in LDS, W_{k+1}[i][j] a pull sum over the raw edges into j (duplicates supply the multiplicity; summed in
+ * 64 bits and clamped to 2^32 - 1, so the order of the terms cannot matter), node sets as ceil(n / 64) words, the rank of a
+ * target in the any-hop mask a prefix popcount over words, the edge-type histogram of the peripheral statistics in 32 bits.
+ *   kpgnn_khop_large_count  per graph of the launch: status[g]; the adjacency into the workspace by two stable counting sorts
+ *                           of its edge slice (positions are counted, never raced for: the workspace is the same bits on
+ *                           every run); per node the any-hop words and the K-hop out-degree.  A node of a graph whose status
+ *                           is not 0 gets degree 0; a graph outside the launch is not written.
+ *   kpgnn_khop_large_fill   the graphs whose status is 0, from the adjacency the count pass left: the outputs of
+ *                           kpgnn_khop_dev_fill, every global write checked against E_out / N; other slices are left alone.
+ * Workspace (kpgnn_khop_large_workspace_bytes(N, E_in, max_nodes); W = ceil(max_nodes / 64); every launch between a count
+ * pass and its fill pass that shares one workspace passes the SAME max_nodes, since W is the stride of the word arrays):
+ *   int64  deg[N]            the K-hop out-degree of each node - what the caller scans, exactly as for the pair above
+ *   uint64 any[N][W]         the any-hop mask of each node, one bit per local target
+ *   uint64 nzt[N][W]         the targets of a node's edges whose summed type is not 0
+ *   int32  in_start[N], in_cnt[N], out_start[N], out_cnt[N]     a node's range in the edge arrays below (positions of the call)
+ *   int32  in_src[E_in]      edges sorted by destination (stable): the source of each
+ *   int32  s_dst[E_in]       ... its destination (scratch of the second sort)
+ *   int32  m_typ[E_in]       edges sorted by (source, destination): the summed type of (u, v) on the first edge of its run of
+ *                            duplicates, 0 on the others (first: the types in the order of in_src)
+ *   int32  o_src[E_in], o_dst[E_in], o_typ[E_in]                edges sorted by (source, destination): source, destination, type
+ * No global atomics, no float, bitwise reproducible.  G == 0 or n_ids == 0 return KPGNN_OK without a launch; ids outside
+ * [0, G) are skipped; edges are read from [edge_ptr[g], edge_ptr[g+1]) clipped to [0, E_in).
+ * ---------------------------------------------------------------------------------------------- */
+#define KPGNN_KHOP_LARGE_MAX_NODES 2048
+
+size_t kpgnn_khop_large_workspace_bytes(int64_t N, int64_t E_in, int32_t max_nodes);
+int kpgnn_khop_large_count(const kpgnn_khop_dev_desc* d, kpgnn_stream_t stream);
+int kpgnn_khop_large_fill(const kpgnn_khop_dev_desc* d, kpgnn_stream_t stream);
 
 #ifdef __cplusplus
 }

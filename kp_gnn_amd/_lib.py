@@ -404,6 +404,7 @@ class RdProjDesc(ctypes.Structure):
 KHOP_OK, KHOP_TOO_LARGE, KHOP_RANGE, KHOP_ENDPOINT, KHOP_TYPE, KHOP_SHAPE = 0, 1, 2, 3, 4, 5    # include/kpgnn.h KPGNN_KHOP_*
 KHOP_MAX_NODES, KHOP_WAVE_NODES, KHOP_MAX_TYPE = 64, 32, 63             # KPGNN_KHOP_MAX_NODES, _WAVE_NODES, _MAX_TYPE
 KHOP_MAX_K, KHOP_MAX_T, KHOP_MAX_H = 16, 8, 8                           # KPGNN_KHOP_MAX_K, _MAX_T, _MAX_H
+KHOP_LARGE_MAX_NODES = 2048                                             # KPGNN_KHOP_LARGE_MAX_NODES (kpgnn_khop_large_*)
 
 
 class KhopDevDesc(ctypes.Structure):
@@ -532,6 +533,9 @@ SIGNATURES = {
     "kpgnn_khop_dev_workspace_bytes": (ctypes.c_size_t, [c_i64]),
     "kpgnn_khop_dev_count": (ctypes.c_int, [ctypes.POINTER(KhopDevDesc), c_vp]),
     "kpgnn_khop_dev_fill": (ctypes.c_int, [ctypes.POINTER(KhopDevDesc), c_vp]),
+    "kpgnn_khop_large_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i64, c_i32]),
+    "kpgnn_khop_large_count": (ctypes.c_int, [ctypes.POINTER(KhopDevDesc), c_vp]),
+    "kpgnn_khop_large_fill": (ctypes.c_int, [ctypes.POINTER(KhopDevDesc), c_vp]),
     "kpgnn_vn_add_pool": (ctypes.c_int, [ctypes.POINTER(VnDesc), c_vp]),
     "kpgnn_dropout_fwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
     "kpgnn_dropout_bwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),

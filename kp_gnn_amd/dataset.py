@@ -54,6 +54,7 @@ class KHopDataset:
     """G pre-transformed graphs in HBM: node / graph attributes in (data, slices) layout + the graph-local K-hop CSR."""
 
     NODES_PER_TILE = KHopCSR.NODES_PER_TILE
+    LARGE_AUTO = "device"    # from_graphs(large="auto"): who serves graphs above 64 nodes (DESIGN.md 5.21 has the measurement)
 
     def __init__(self):
         self.node_rows = {}      # name -> [Nd, ...] device tensor gathered per batch node (x, z, ...)
@@ -111,7 +112,7 @@ class KHopDataset:
 
     @staticmethod
     def from_graphs(node_ptr, edge_ptr, edge_index, edge_attr, device, khop_args, x=None, z=None, y=None, chunk_graphs=4096,
-                    with_entry_lists=True, with_rd=False, route="auto"):
+                    with_entry_lists=True, with_rd=False, route="auto", large="auto"):
         """The dataset from RAW graphs: node_ptr / edge_ptr [G+1] host offsets, edge_index [2,E] LOCAL ids and edge_attr [E] or
         None (what khop_transform.khop_batch takes), khop_args = (K, max_edge_attr_num, max_hop_num, max_edge_type,
         max_edge_count, max_distance_count, kernel); x / z [N, ...] node and y [G, ...] graph attributes.
@@ -119,9 +120,15 @@ class KHopDataset:
         graph its kernel does not serve takes the host route inside that call), then KHopCSR.build on the tensors where they
         lie, then the rd column if asked; the dictionary comes from the device peripheral tensors.  route "host":
         khop_batch + from_collated.  "auto" is the device route: DESIGN.md 5.20 has the measurement behind it.  Either route
-        gives the same dataset, bit for bit."""
+        gives the same dataset, bit for bit.
+        large (the device route only): who serves a graph of more than 64 nodes inside ops.khop_transform - "device" the
+        kernels of csrc/khop_large.hip (up to KHOP_LARGE_MAX_NODES nodes), "host" khop_batch; "auto" is LARGE_AUTO, which
+        DESIGN.md 5.21 decides from a measurement.  The dataset is the same bit for bit whichever is chosen."""
         if route not in ("auto", "device", "host"):
             raise ValueError(f"unknown route {route!r}")
+        if large not in ("auto", "device", "host"):
+            raise ValueError(f"unknown large {large!r}")
+        large = KHopDataset.LARGE_AUTO if large == "auto" else large
         from . import khop_transform as KT
         node_ptr, edge_ptr = np.asarray(node_ptr, dtype=np.int64), np.asarray(edge_ptr, dtype=np.int64)
         as_t = lambda a: a if a is None or torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
@@ -146,7 +153,7 @@ class KHopDataset:
             g1 = min(G, g0 + chunk_graphs)
             n0, e0, e1 = int(node_ptr[g0]), int(edge_ptr[g0]), int(edge_ptr[g1])
             out, _ = khop_transform(node_ptr[g0:g1 + 1] - n0, edge_ptr[g0:g1 + 1] - e0, edge_index[:, e0:e1],
-                                    None if edge_attr is None else edge_attr[e0:e1], *khop_args, ds.device)
+                                    None if edge_attr is None else edge_attr[e0:e1], *khop_args, ds.device, large=large)
             k_eptr = out["edge_ptr"].cpu().numpy()
             edge_cnt.append(np.diff(k_eptr))
             ds._add_chunk(acc, out["edge_index"], out["edge_attr"], node_ptr[g0:g1 + 1] - n0, k_eptr)

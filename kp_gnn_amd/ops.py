@@ -2208,7 +2208,7 @@ def resistance_distance(node_ptr, edge_ptr, edge_index, device):
 
 # ------------------------------------------------------------------------------------------------ the K-hop pre-transform
 def khop_transform(node_ptr, edge_ptr, edge_index, edge_attr, K, max_edge_attr_num, max_hop_num, max_edge_type,
-                   max_edge_count, max_distance_count, kernel, device):
+                   max_edge_count, max_distance_count, kernel, device, large="host"):
     """khop_transform.khop_batch on the device: (the same dict of collated int64 tensors, on `device`; status [G] int32 on the
     host).  node_ptr / edge_ptr [G+1]: host offsets; edge_index [2,E] LOCAL ids and edge_attr [E] or None, host or device.
     The graphs are bucketed by size (n <= 32: a wavefront per graph; n <= 64: a block per graph), kpgnn_khop_dev_count runs per
@@ -2216,7 +2216,13 @@ def khop_transform(node_ptr, edge_ptr, edge_index, edge_attr, K, max_edge_attr_n
     kpgnn_khop_dev_fill writes the tensors.  Graphs the kernel did not serve - more than 64 nodes (1), a summed edge type above
     63 (4), K / max_edge_type / max_hop_num beyond 16 / 8 / 8 (5) - go through khop_batch on the host: their edge counts join
     the scan and their slices are copied in, so the result is the same whichever route served a graph.  A walk count >= 2^31
-    (2) raises what khop_batch raises for that graph (KpgnnError), an edge endpoint outside its graph (3) ValueError."""
+    (2) raises what khop_batch raises for that graph (KpgnnError), an edge endpoint outside its graph (3) ValueError.
+    large="device": the graphs of more than 64 and at most KHOP_LARGE_MAX_NODES nodes are a third class, served inside the same
+    call by kpgnn_khop_large_count / _fill (a wavefront per source row, csrc/khop_large.hip): their degrees join the same scan
+    and the same read, their status is 0, and only graphs above that cap, 4 and 5 go to the host.  "host", the default, leaves
+    every graph above 64 nodes to khop_batch.  The tensors are the same bits either way."""
+    if large not in ("host", "device"):
+        raise ValueError(f"unknown large {large!r}: 'host' or 'device'")
     from . import khop_transform as KT
     node_ptr, edge_ptr = _host_i64(node_ptr), _host_i64(edge_ptr)
     G = node_ptr.shape[0] - 1
@@ -2260,18 +2266,30 @@ def khop_transform(node_ptr, edge_ptr, edge_index, edge_attr, K, max_edge_attr_n
     d.kernel = 0 if kernel == "spd" else 1
     d.workspace, d.workspace_bytes, d.status = ws.data_ptr(), ws.numel() * 8, st.data_ptr()
     classes = []
-    for ids in (np.flatnonzero(nodes <= _lib.KHOP_WAVE_NODES), np.flatnonzero(nodes > _lib.KHOP_WAVE_NODES)):
+    block = nodes > _lib.KHOP_WAVE_NODES
+    if large == "device":
+        block &= nodes <= _lib.KHOP_MAX_NODES
+    for ids in (np.flatnonzero(nodes <= _lib.KHOP_WAVE_NODES), np.flatnonzero(block)):
         if ids.size:
-            classes.append((torch.from_numpy(ids.astype(np.int32)).to(dev), ids.size,
-                            max(1, min(_lib.KHOP_MAX_NODES, int(nodes[ids].max())))))     # (larger graphs get status 1)
+            classes.append(("kpgnn_khop_dev", torch.from_numpy(ids.astype(np.int32)).to(dev), ids.size,
+                            max(1, min(_lib.KHOP_MAX_NODES, int(nodes[ids].max()))), ws))  # (larger graphs get status 1)
+    ws_l = None
+    ids = np.flatnonzero(nodes > _lib.KHOP_MAX_NODES) if large == "device" else np.zeros(0, np.int64)
+    if ids.size:                                            # the third class: its own pair, its own workspace, degrees in front
+        cap = int(nodes[ids][nodes[ids] <= _lib.KHOP_LARGE_MAX_NODES].max(initial=_lib.KHOP_MAX_NODES + 1))
+        ws_l = torch.zeros(_lib.load().kpgnn_khop_large_workspace_bytes(N, E, cap) // 8, **i64)
+        classes.append(("kpgnn_khop_large", torch.from_numpy(ids.astype(np.int32)).to(dev), ids.size, cap, ws_l))
 
-    def run(name):
-        for ids_d, n_ids, cap in classes:
+    def run(pass_):
+        for pair, ids_d, n_ids, cap, w in classes:
             d.graph_ids, d.n_ids, d.max_nodes = ids_d.data_ptr(), n_ids, cap
-            _lib.launch(name, dev, ctypes.byref(d), timed=("khop_dev", lambda: 0))
+            d.workspace, d.workspace_bytes = w.data_ptr(), w.numel() * 8
+            _lib.launch(pair + pass_, dev, ctypes.byref(d), timed=("khop_dev", lambda: 0))
 
-    run("kpgnn_khop_dev_count")
+    run("_count")
     deg = ws[N:2 * N]
+    if ws_l is not None:
+        deg += ws_l[:N]                                     # (0 wherever the large pair did not serve)
     run_sum = torch.cat([deg.new_zeros(1), deg.cumsum(0)])
     back = torch.cat([st.long(), run_sum[nptr[1:]] - run_sum[nptr[:-1]]]).cpu().numpy()         # the one read
     status, g_edges = back[:G].astype(np.int32), back[G:].copy()
@@ -2310,7 +2328,7 @@ def khop_transform(node_ptr, edge_ptr, edge_index, edge_attr, K, max_edge_attr_n
     d.out_edge_index, d.out_edge_attr, d.out_pe_attr = ptr(out["edge_index"]), ptr(out["edge_attr"]), ptr(out["pe_attr"])
     d.out_pea, d.out_pca = ptr(out["peripheral_edge_attr"]), ptr(out["peripheral_configuration_attr"])
     d.out_batch = ptr(out["batch"])
-    run("kpgnn_khop_dev_fill")
+    run("_fill")
     if host is not None:
         h_off = host["edge_ptr"].numpy()
         e_dst = np.concatenate([np.arange(out_eptr[g], out_eptr[g + 1]) for g in todo])

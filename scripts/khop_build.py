@@ -13,7 +13,16 @@ per round after one warm-up of each:
 Every figure is a host clock around work that ends in a device synchronise; the device route's launches are also bracketed by
 HIP events (_lib.LaunchTimer) and their sum is reported as `device_launches_s`.  A round's datasets are compared tensor for
 tensor once.  Reported: the median over the rounds and the spread (min .. max) of khop_batch, from_collated, their sum and
-from_graphs, and `auto` - "device" when from_graphs' median is below the host route's sum, "host" otherwise."""
+from_graphs, and `auto` - "device" when from_graphs' median is below the host route's sum, "host" otherwise.
+
+Two more workloads (`--workloads regular1280,tu_mixed`; `--graphs` does not apply) measure who should serve graphs above 64
+nodes INSIDE the device route - from_graphs(route="device", large="host"), where ops.khop_transform hands them to khop_batch
+and copies the slices in, against large="device", the kernels of csrc/khop_large.hip:
+    regular1280   100 random 3-regular graphs of 1280 nodes with run_simulation.py's arguments (8, 10, 1, 1, 1, 1, "spd"), no
+                  edge types;
+    tu_mixed      2,000 seeded random graphs of 20 .. 620 nodes, mean degree 4, (3, 50, 3, 1, 50, 50, "gd").
+Same process, same alternation, same comparison; `device_wins` is true when the device leg's median is below the host leg's by
+more than the host leg's spread between rounds (max - min)."""
 import argparse
 import json
 import os
@@ -25,6 +34,24 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 WORKLOADS = {"zinc": ("zinc", (8, 50, 6, 3, 50, 50, "spd")), "zinc_gd16": ("zinc", (16, 50, 6, 3, 50, 50, "gd")),
              "qm9": ("qm9", (6, 50, 5, 4, 20, 15, "spd"))}
+
+
+LARGE_WORKLOADS = {"regular1280": (8, 10, 1, 1, 1, 1, "spd"), "tu_mixed": (3, 50, 3, 1, 50, 50, "gd")}
+
+
+def large_graphs(name):
+    """(node_ptr, edge_ptr, edge_index [2,E] local ids) of a LARGE_WORKLOADS entry; every edge in both directions, no types."""
+    import networkx as nx
+    import numpy as np
+    if name == "regular1280":
+        graphs = [nx.random_regular_graph(3, 1280, seed=s) for s in range(100)]
+    else:
+        sizes = np.random.default_rng(1).integers(20, 621, size=2000)
+        graphs = [nx.gnm_random_graph(int(n), 2 * int(n), seed=s) for s, n in enumerate(sizes)]
+    eis = [np.array(sorted(g.to_directed().edges), dtype=np.int64).reshape(-1, 2).T for g in graphs]
+    node_ptr = np.cumsum([0] + [g.number_of_nodes() for g in graphs]).astype(np.int64)
+    edge_ptr = np.cumsum([0] + [e.shape[1] for e in eis]).astype(np.int64)
+    return node_ptr, edge_ptr, np.ascontiguousarray(np.concatenate(eis, axis=1))
 
 
 def spread(v):
@@ -61,6 +88,45 @@ def main():
     threads = args.threads or usable_cpus()
     res = dict(graphs=args.graphs, threads=threads, device=torch.cuda.get_device_name(0), workloads={})
     for name in args.workloads.split(","):
+        if name in LARGE_WORKLOADS:
+            kargs = LARGE_WORKLOADS[name]
+            node_ptr, edge_ptr, ei = large_graphs(name)
+            xt = torch.ones(int(node_ptr[-1]), 1)
+
+            def leg(large):
+                timer = _lib.LaunchTimer()
+                _lib.set_launch_timer(timer)
+                try:
+                    t0 = time.perf_counter()
+                    ds = KHopDataset.from_graphs(node_ptr, edge_ptr, ei, None, dev, kargs, x=xt, route="device", large=large)
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                finally:
+                    _lib.set_launch_timer(None)
+                return ds, dt, sum(a.elapsed_time(b) for kind, _, a, b in timer.records if kind == "khop_dev") * 1e-3
+
+            torch.set_num_threads(threads)
+            a, b = leg("host")[0], leg("device")[0]                     # warm-up of each leg and the one comparison
+            identical = all(same(u, v) for u, v in zip(a.state(), b.state()))
+            khop_edges = int(a.h_edges.sum())
+            del a, b
+            t_host, t_dev, t_launch = [], [], []
+            for _ in range(args.rounds):
+                t_host.append(leg("host")[1])
+                _, td, tl = leg("device")
+                t_dev.append(td), t_launch.append(tl)
+            n = node_ptr[1:] - node_ptr[:-1]
+            entry = dict(args=list(kargs), graphs=int(n.size), nodes=int(node_ptr[-1]), input_edges=int(edge_ptr[-1]),
+                         khop_edges=khop_edges, min_nodes=int(n.min()), max_nodes=int(n.max()), graphs_above_64=int((n > 64).sum()),
+                         large_host_s=spread(t_host), large_device_s=spread(t_dev), device_launches_s=spread(t_launch),
+                         identical=identical)
+            h, d = entry["large_host_s"], entry["large_device_s"]
+            entry["device_wins"] = bool(h["median"] - d["median"] > h["max"] - h["min"])
+            res["workloads"][name] = entry
+            print(f"[khop_build] {name}: large=host {h['median']:.3f} s ({h['min']:.3f} .. {h['max']:.3f}), large=device "
+                  f"{d['median']:.3f} s ({d['min']:.3f} .. {d['max']:.3f}; launches {entry['device_launches_s']['median']:.4f}), "
+                  f"identical={identical}, device_wins={entry['device_wins']}", file=sys.stderr, flush=True)
+            continue
         shape, kargs = WORKLOADS[name]
         node_ptr, edge_ptr, ei, ea, x = KT.synth_molecules(args.graphs, 1, shape=KT.qm9_shape() if shape == "qm9" else None)
         xt = torch.from_numpy(x).view(-1, 1)
