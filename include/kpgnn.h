@@ -1532,6 +1532,32 @@ size_t kpgnn_khop_large_workspace_bytes(int64_t N, int64_t E_in, int32_t max_nod
 int kpgnn_khop_large_count(const kpgnn_khop_dev_desc* d, kpgnn_stream_t stream);
 int kpgnn_khop_large_fill(const kpgnn_khop_dev_desc* d, kpgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Embedding collisions of the regular-graph simulation (csrc/collisions.hip; run_simulation.py:165-178,
+ * compute_simulation_collisions).  For the rows o[i,:] of x [N,D] fp32, d2(i,j) = sum_d (o[i,d] - o[j,d])^2 evaluated in fp32
+ * in the difference form (never |a|^2 + |b|^2 - 2 a.b), and a pair collides iff d2 < eps by the plain IEEE compare:
+ *   out[0] = upper = #{ i < j : d2(i,j) < eps }
+ *   out[1] = diag  = #{ i : d2(i,i) < eps }        (the rows without a NaN or Inf, since x - x is 0 or NaN; 0 when eps == 0)
+ * so the reference's (diff < eps).sum() is 2 * upper + diag.  Both are exact integers; the order of the partial sums cannot
+ * matter.  A pair whose exact d2 lies outside [eps (1 - delta), eps (1 + delta)], delta = (D + 2) 2^-23, is classified as exact
+ * arithmetic classifies it (derivation: csrc/collisions.hip).  The pair matrix is walked as 128 x 128 tiles of its upper
+ * triangle by a persistent grid; every block leaves one pair of 64-bit partial counts in the workspace and a second, one-block
+ * launch adds them into `out`: two launches, no atomics, nothing read back.  Rows are read in place through x_stride.
+ * 1 <= D <= 256, eps finite and >= 0, workspace 8-byte aligned (KPGNN_EINVAL otherwise).  N == 0 returns KPGNN_OK without a
+ * launch and leaves `out` alone.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct kpgnn_collision_desc {
+    int64_t N;                  /* rows */
+    int32_t D;                  /* columns, 1 .. 256 */
+    float eps;                  /* threshold on the squared distance (the reference's 1e-10) */
+    const float* x; int64_t x_stride;      /* device [N,D], unit column stride, x_stride >= D floats between rows */
+    int64_t* out;               /* device int64[2]: upper, diag */
+    void* workspace; int64_t workspace_bytes;      /* device, >= kpgnn_collision_workspace_bytes(N) */
+} kpgnn_collision_desc;
+
+int64_t kpgnn_collision_workspace_bytes(int64_t N);
+int kpgnn_collision_count(const kpgnn_collision_desc* d, kpgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

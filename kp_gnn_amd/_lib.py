@@ -419,6 +419,16 @@ class KhopDevDesc(ctypes.Structure):
     ]
 
 
+class CollisionDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("D", c_i32), ("eps", ctypes.c_float),
+        ("x", c_vp), ("x_stride", c_i64), ("out", c_vp), ("workspace", c_vp), ("workspace_bytes", c_i64),
+    ]
+
+
+COLLISION_MAX_D = 256                                                   # csrc/collisions.hip kMaxD
+
+
 class AttnPoolDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i64), ("G", c_i32), ("D", c_i32),
@@ -536,6 +546,8 @@ SIGNATURES = {
     "kpgnn_khop_large_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i64, c_i32]),
     "kpgnn_khop_large_count": (ctypes.c_int, [ctypes.POINTER(KhopDevDesc), c_vp]),
     "kpgnn_khop_large_fill": (ctypes.c_int, [ctypes.POINTER(KhopDevDesc), c_vp]),
+    "kpgnn_collision_workspace_bytes": (c_i64, [c_i64]),
+    "kpgnn_collision_count": (ctypes.c_int, [ctypes.POINTER(CollisionDesc), c_vp]),
     "kpgnn_vn_add_pool": (ctypes.c_int, [ctypes.POINTER(VnDesc), c_vp]),
     "kpgnn_dropout_fwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
     "kpgnn_dropout_bwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),

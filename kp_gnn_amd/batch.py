@@ -82,10 +82,10 @@ def synthetic_qm9_batch(num_graphs, seed0, K=6, kernel="spd", num_threads=0):
     return b
 
 
-def synthetic_regular_batch(num_graphs, seed0, n=1280, degree=3, K=8, num_threads=0):
-    """run_simulation.py's workload (:96-129): `num_graphs` random `degree`-regular graphs on n nodes
-    (nx.random_regular_graph(d, n, seed), seeds seed0, seed0+1, ..), x = ones [n,1], pre-transform arguments
-    (k, 10, 1, 1, 1, 1, "spd") (:103)."""
+def regular_graphs(num_graphs, seed0, n=1280, degree=3):
+    """run_simulation.py's generator (:119-129): `num_graphs` random `degree`-regular graphs on n nodes
+    (nx.random_regular_graph(d, n, seed), seeds seed0, seed0+1, ..) as raw graphs: (node_ptr [G+1], edge_ptr [G+1],
+    edge_index [2,E] with LOCAL ids), numpy int64."""
     import networkx as nx
     import numpy as np
     eis, node_ptr, edge_ptr = [], [0], [0]
@@ -96,6 +96,12 @@ def synthetic_regular_batch(num_graphs, seed0, n=1280, degree=3, K=8, num_thread
         node_ptr.append(node_ptr[-1] + n)
         edge_ptr.append(edge_ptr[-1] + e.shape[1])
     ei = np.ascontiguousarray(np.concatenate(eis, axis=1))
+    return np.array(node_ptr, dtype=np.int64), np.array(edge_ptr, dtype=np.int64), ei
+
+
+def synthetic_regular_batch(num_graphs, seed0, n=1280, degree=3, K=8, num_threads=0):
+    """run_simulation.py's workload (:96-129): the graphs of regular_graphs, x = ones [n,1], pre-transform arguments
+    (k, 10, 1, 1, 1, 1, "spd") (:103)."""
+    node_ptr, edge_ptr, ei = regular_graphs(num_graphs, seed0, n=n, degree=degree)
     x = torch.ones(num_graphs * n, 1)
-    return collate_khop(np.array(node_ptr, dtype=np.int64), np.array(edge_ptr, dtype=np.int64), ei, None, x,
-                        (K, 10, 1, 1, 1, 1, "spd"), num_threads=num_threads)
+    return collate_khop(node_ptr, edge_ptr, ei, None, x, (K, 10, 1, 1, 1, 1, "spd"), num_threads=num_threads)

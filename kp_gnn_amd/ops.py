@@ -2586,3 +2586,89 @@ def enc_tables(squash, encoders):
     enc_t = [t for (w, b, g, _, _) in encoders for t in (w, b, g)]
     embs = [e for (_, _, _, _, es) in encoders for e in es]
     return EncTables.apply(squash, mults, ncomps, *enc_t, *embs)
+
+
+# ------------------------------------------------------------------------------------------------ embedding collisions
+# The result of the regular-graph simulation (run_simulation.py:165-178): how many pairs of rows of an [N,D] matrix lie within
+# sqrt(eps) of each other.  Device fp32 rows of up to 256 columns take kpgnn_collision_count (two launches, 64-bit counts, the
+# pair matrix never exists); everything else takes the same count as a blocked framework expression.
+_NATIVE_COLLISIONS = True
+_COLLISION_BLOCK = 2048        # rows of a block of the framework expression: one [2048, 2048] fp32 block of pairs at a time
+
+
+def set_native_collisions(on):
+    """Route collision_count of fp32 device rows with D <= 256 through kpgnn_collision_count (True) or keep the blocked framework
+    expression (False).  Returns the previous setting."""
+    global _NATIVE_COLLISIONS
+    prev, _NATIVE_COLLISIONS = _NATIVE_COLLISIONS, bool(on)
+    return prev
+
+
+def native_collisions():
+    return _NATIVE_COLLISIONS
+
+
+def collision_count_applies(outputs):
+    """Whether collision_count takes the native route: the switch is on and `outputs` is a device fp32 [N,D] tensor, D <= 256."""
+    return bool(_NATIVE_COLLISIONS and outputs.is_cuda and outputs.dtype == torch.float32 and outputs.dim() == 2
+                and 1 <= outputs.shape[1] <= _lib.COLLISION_MAX_D)
+
+
+def collision_count_reference(outputs, epsilon=1e-10, block=None):
+    """(upper, diag) as 0-dim int64 tensors on the device of `outputs`, by the framework expression on blocks of `block` rows:
+    d2 accumulates (a[:, d, None] - b[None, :, d])^2 over d in fp32 for one block of pairs at a time (the reference's
+    [N, D, N] tensor never exists), d2 < epsilon is counted above the diagonal and on it.  Subtract, square and add are rounded
+    separately, 3u per term and (D - 1)u for the sum with u = 2^-24: inside the same band as the kernel (csrc/collisions.hip)."""
+    block = int(block or _COLLISION_BLOCK)
+    o = outputs.detach().to(torch.float32)
+    N, D = o.shape
+    upper = torch.zeros((), dtype=torch.int64, device=o.device)
+    diag = torch.zeros((), dtype=torch.int64, device=o.device)
+    for i0 in range(0, N, block):
+        a = o[i0:i0 + block]
+        for j0 in range(i0, N, block):
+            b = o[j0:j0 + block]
+            d2 = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.float32, device=o.device)
+            for d in range(D):
+                diff = a[:, d, None] - b[None, :, d]
+                d2 += diff * diff
+            hit = d2 < epsilon
+            if i0 == j0:
+                upper += torch.triu(hit, diagonal=1).sum()
+                diag += hit.diagonal().sum()
+            else:
+                upper += hit.sum()
+    return upper, diag
+
+
+def _collision_count_launch(o, epsilon):
+    """int64[2] device tensor (upper, diag) of fp32 device rows o [N,D], N >= 1: one kpgnn_collision_count call (two launches).
+    A strided o with unit column stride is read in place."""
+    N, D = o.shape
+    o = _rows_view(o, D)
+    out = torch.empty(2, dtype=torch.int64, device=o.device)
+    nbytes = _lib.load().kpgnn_collision_workspace_bytes(N)
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=o.device)
+    d = _lib.CollisionDesc()
+    d.N, d.D, d.eps = N, D, float(epsilon)
+    d.x, d.x_stride, d.out, d.workspace, d.workspace_bytes = o.data_ptr(), o.stride(0), out.data_ptr(), ws.data_ptr(), nbytes
+    _lib.launch("kpgnn_collision_count", o.device, ctypes.byref(d))
+    return out
+
+
+def collision_count(outputs, epsilon=1e-10):
+    """(upper, diag) as Python ints for the rows of `outputs` [N,D]: upper = #{i < j : d2(i,j) < epsilon}, diag = #{i : d2(i,i) <
+    epsilon} with d2 the squared distance in fp32 and epsilon compared as fp32 (run_simulation.py:166-173, whose count
+    (diff < epsilon).sum() is 2 * upper + diag).  One read-back.  Where collision_count_applies: kpgnn_collision_count.
+    Everything else - CPU tensors, other dtypes (cast to fp32), D > 256, the switch off - takes collision_count_reference."""
+    if outputs.dim() != 2:
+        raise ValueError(f"collision_count needs an [N,D] matrix, got {tuple(outputs.shape)}")
+    N = outputs.shape[0]
+    if N == 0:
+        return 0, 0
+    if N >= 2 and collision_count_applies(outputs):
+        both = _collision_count_launch(outputs.detach(), epsilon)
+    else:                                       # (a single row has only its diagonal: no launch of ours for it)
+        both = torch.stack(collision_count_reference(outputs, epsilon))
+    upper, diag = both.tolist()
+    return int(upper), int(diag)
