@@ -1366,7 +1366,8 @@ int kpgnn_body_norm_bwd(const kpgnn_norm_desc* d, kpgnn_stream_t stream);
  * status[g] (written for every graph of `graph_ids`; out is written only where it is 0):
  *   KPGNN_RD_OK 0          served
  *   KPGNN_RD_ASYMMETRIC 1  A != A^T: a directed list, the host route's job
- *   KPGNN_RD_TOO_LARGE 2   n > max_nodes of this launch (the cap of any launch is 128: one 128 x 129 double matrix in LDS)
+ *   KPGNN_RD_TOO_LARGE 2   n > max_nodes of this launch (the cap of any launch is 128: one 128 x 129 double matrix in LDS;
+ *                          kpgnn_resistance_distance_large below serves up to 2048 nodes from a workspace)
  *   KPGNN_RD_PIVOT 3       a pivot <= 0 or not finite
  *   KPGNN_RD_RANGE 4       an edge endpoint outside [node_ptr[g], node_ptr[g+1])
  * One launch serves the graphs `graph_ids[0 .. n_ids)`.  max_nodes <= 32: one wavefront per graph, four graphs per block, no
@@ -1393,6 +1394,38 @@ typedef struct kpgnn_rd_desc {
 } kpgnn_rd_desc;
 
 int kpgnn_resistance_distance(const kpgnn_rd_desc* d, kpgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The same feature for graphs of up to KPGNN_RD_LARGE_MAX_NODES nodes (csrc/resistance_large.hip).  The mathematics, the
+ * output and the status codes are those of kpgnn_resistance_distance; KPGNN_RD_TOO_LARGE is n > max_nodes of this launch, whose
+ * cap is 2048.  One workgroup of 1024 threads per graph of `graph_ids`; the graph's matrix lives in a slab of `workspace` that
+ * only this workgroup touches (slot i of graph_ids owns slab i), not in LDS: integer counts by global integer atomics,
+ * connected components by hooking over the edge list, M^-1 in place by a BLOCKED Gauss-Jordan sweep without pivoting (panel
+ * width 32, the diagonal block inverted in LDS, plain double FMAs in a fixed order).  No float atomics, no communication between
+ * workgroups: a graph's bits depend on the graph alone, not on the batch, the chunking or the workspace around it.
+ * kpgnn_rd_large_workspace_bytes(max_nodes, n_ids): the bytes a launch of n_ids graphs sized for max_nodes needs - n_ids slabs
+ * of the matrix (rows padded to the panel width) and two panels; 0 for max_nodes outside 1 .. 2048 or n_ids < 0.  `workspace`
+ * (8-byte aligned) need not be zeroed.  The argument checks are those of kpgnn_resistance_distance, then max_nodes > 2048 is
+ * KPGNN_ELIMIT and a NULL or too small workspace KPGNN_EINVAL, all before any device call.
+ * ---------------------------------------------------------------------------------------------- */
+#define KPGNN_RD_LARGE_MAX_NODES 2048
+
+typedef struct kpgnn_rd_large_desc {
+    int32_t G, n_ids;           /* graphs of the call; graphs this launch serves */
+    const int64_t* node_ptr;    /* device [G+1] */
+    const int64_t* edge_ptr;    /* device [G+1] */
+    const int64_t* edge_index;  /* device [2,E] contiguous: global ids within the call, edges grouped by graph */
+    int64_t E;                  /* edges of the call (the row length of edge_index) */
+    const int32_t* graph_ids;   /* device [n_ids] */
+    int32_t max_nodes, reserved;/* largest n this launch is sized for, 1 .. 2048; 0 */
+    float* out;                 /* device [N] */
+    int32_t* status;            /* device [G] */
+    void* workspace;            /* device, >= kpgnn_rd_large_workspace_bytes(max_nodes, n_ids) */
+    size_t workspace_bytes;
+} kpgnn_rd_large_desc;
+
+size_t kpgnn_rd_large_workspace_bytes(int32_t max_nodes, int32_t n_ids);
+int kpgnn_resistance_distance_large(const kpgnn_rd_large_desc* d, kpgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The bodies' resistance-distance projection (csrc/rd_proj.hip; models/GNNs.py `x = x + self.rd_projection(rd)`, an

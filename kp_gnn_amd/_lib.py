@@ -382,6 +382,7 @@ class NormDesc(ctypes.Structure):
 RD_OK, RD_ASYMMETRIC, RD_TOO_LARGE, RD_PIVOT, RD_RANGE = 0, 1, 2, 3, 4    # include/kpgnn.h KPGNN_RD_*
 RD_MAX_NODES, RD_WAVE_NODES = 128, 32                                   # KPGNN_RD_MAX_NODES, KPGNN_RD_WAVE_NODES
 RD_PROJ_MAX_H = 256                                                     # csrc/rd_proj.hip kMaxH
+RD_LARGE_MAX_NODES = 2048                                               # KPGNN_RD_LARGE_MAX_NODES (kpgnn_resistance_distance_large)
 
 
 class RdDesc(ctypes.Structure):
@@ -389,6 +390,10 @@ class RdDesc(ctypes.Structure):
         ("G", c_i32), ("n_ids", c_i32), ("node_ptr", c_vp), ("edge_ptr", c_vp), ("edge_index", c_vp), ("E", c_i64),
         ("graph_ids", c_vp), ("max_nodes", c_i32), ("reserved", c_i32), ("out", c_vp), ("status", c_vp),
     ]
+
+
+class RdLargeDesc(ctypes.Structure):
+    _fields_ = RdDesc._fields_ + [("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t)]
 
 
 class RdProjDesc(ctypes.Structure):
@@ -537,6 +542,8 @@ SIGNATURES = {
     "kpgnn_segment_max_fwd": (ctypes.c_int, [ctypes.POINTER(PoolMaxDesc), c_vp]),
     "kpgnn_segment_max_bwd": (ctypes.c_int, [ctypes.POINTER(PoolMaxDesc), c_vp]),
     "kpgnn_resistance_distance": (ctypes.c_int, [ctypes.POINTER(RdDesc), c_vp]),
+    "kpgnn_rd_large_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
+    "kpgnn_resistance_distance_large": (ctypes.c_int, [ctypes.POINTER(RdLargeDesc), c_vp]),
     "kpgnn_rd_proj_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i32]),
     "kpgnn_rd_proj_fwd": (ctypes.c_int, [ctypes.POINTER(RdProjDesc), c_vp]),
     "kpgnn_rd_proj_bwd": (ctypes.c_int, [ctypes.POINTER(RdProjDesc), c_vp]),

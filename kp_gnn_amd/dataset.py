@@ -65,13 +65,18 @@ class KHopDataset:
 
     # ------------------------------------------------------------------------------------------------ construction
     @staticmethod
-    def from_collated(batch, node_ptr, device, chunk_graphs=4096, with_entry_lists=True, with_rd=False):
+    def from_collated(batch, node_ptr, device, chunk_graphs=4096, with_entry_lists=True, with_rd=False, rd_large="host"):
         """`batch`: a HOST KHopBatch holding ALL graphs collated (batch.collate_khop: the reference's pre_transform output in
         PyG's concatenated layout); node_ptr [G+1] its slices.  The CSR is built chunk by chunk on the device.
         with_rd: also compute the resistance-distance node feature (`--use_rd`) per chunk with ops.resistance_distance from the
         chunk's K-hop edge list, which is on the device anyway - the reference computes it AFTER its K-hop transform too
         (train_qm9.py:241) - and keep it as node_rows["rd"] [Nd,1] float32, so that every collated batch has `.rd`.  A
-        `batch.rd` that is already there is carried as given, whatever with_rd says."""
+        `batch.rd` that is already there is carried as given, whatever with_rd says.
+        rd_large: ops.resistance_distance's `large` - who computes that column for a graph of more than 128 nodes: "host" the
+        float64 host route, "device" csrc/resistance_large.hip (up to RD_LARGE_MAX_NODES nodes).  Two float64 computations: the
+        float32 rows they give may differ in the last bit, which is why this is not from_graphs' `large`."""
+        if rd_large not in ("host", "device"):
+            raise ValueError(f"unknown rd_large {rd_large!r}")
         if batch.edge_index.is_cuda:
             raise ValueError("from_collated expects the host-side collated dataset")
         ds = KHopDataset()
@@ -95,7 +100,7 @@ class KHopDataset:
         edge_cnt = np.diff(edge_ptr)
         dev = ds.device
         given_rd = getattr(batch, "rd", None)
-        acc = ds._begin(with_entry_lists, with_rd and given_rd is None)
+        acc = ds._begin(with_entry_lists, with_rd and given_rd is None, rd_large)
         for g0 in range(0, G, chunk_graphs):
             g1 = min(G, g0 + chunk_graphs)
             n0, e0, e1 = int(node_ptr[g0]), int(edge_ptr[g0]), int(edge_ptr[g1])
@@ -112,7 +117,7 @@ class KHopDataset:
 
     @staticmethod
     def from_graphs(node_ptr, edge_ptr, edge_index, edge_attr, device, khop_args, x=None, z=None, y=None, chunk_graphs=4096,
-                    with_entry_lists=True, with_rd=False, route="auto", large="auto"):
+                    with_entry_lists=True, with_rd=False, route="auto", large="auto", rd_large="host"):
         """The dataset from RAW graphs: node_ptr / edge_ptr [G+1] host offsets, edge_index [2,E] LOCAL ids and edge_attr [E] or
         None (what khop_transform.khop_batch takes), khop_args = (K, max_edge_attr_num, max_hop_num, max_edge_type,
         max_edge_count, max_distance_count, kernel); x / z [N, ...] node and y [G, ...] graph attributes.
@@ -123,11 +128,15 @@ class KHopDataset:
         gives the same dataset, bit for bit.
         large (the device route only): who serves a graph of more than 64 nodes inside ops.khop_transform - "device" the
         kernels of csrc/khop_large.hip (up to KHOP_LARGE_MAX_NODES nodes), "host" khop_batch; "auto" is LARGE_AUTO, which
-        DESIGN.md 5.21 decides from a measurement.  The dataset is the same bit for bit whichever is chosen."""
+        DESIGN.md 5.21 decides from a measurement.  The dataset is the same bit for bit whichever is chosen.
+        rd_large (with_rd, either route): from_collated's keyword of that name, the `large` of the per-chunk
+        ops.resistance_distance."""
         if route not in ("auto", "device", "host"):
             raise ValueError(f"unknown route {route!r}")
         if large not in ("auto", "device", "host"):
             raise ValueError(f"unknown large {large!r}")
+        if rd_large not in ("host", "device"):
+            raise ValueError(f"unknown rd_large {rd_large!r}")
         large = KHopDataset.LARGE_AUTO if large == "auto" else large
         from . import khop_transform as KT
         node_ptr, edge_ptr = np.asarray(node_ptr, dtype=np.int64), np.asarray(edge_ptr, dtype=np.int64)
@@ -142,12 +151,12 @@ class KHopDataset:
                            peripheral_configuration_attr=out["peripheral_configuration_attr"], batch=out["batch"],
                            num_graphs=node_ptr.shape[0] - 1)
             hb.edge_ptr = out["edge_ptr"].numpy()
-            return KHopDataset.from_collated(hb, node_ptr, device, chunk_graphs, with_entry_lists, with_rd)
+            return KHopDataset.from_collated(hb, node_ptr, device, chunk_graphs, with_entry_lists, with_rd, rd_large)
         from .ops import khop_transform
         ds = KHopDataset()
         G = node_ptr.shape[0] - 1
         ds.G, ds.K, ds.device = G, int(khop_args[0]), torch.device(device)
-        acc = ds._begin(with_entry_lists, with_rd)
+        acc = ds._begin(with_entry_lists, with_rd, rd_large)
         edge_cnt, peas, pcas = [], [], []
         for g0 in range(0, G, chunk_graphs):
             g1 = min(G, g0 + chunk_graphs)
@@ -167,11 +176,11 @@ class KHopDataset:
             ds._build_dictionary(torch.cat(peas), torch.cat(pcas))
         return ds
 
-    def _begin(self, with_entry_lists, with_rd):
+    def _begin(self, with_entry_lists, with_rd, rd_large="host"):
         """What the chunks of a construction add up to (_add_chunk) before _finish joins them; with_rd: every chunk also
-        computes the resistance-distance column from its K-hop edge list."""
+        computes the resistance-distance column from its K-hop edge list, rd_large the `large` of that call."""
         return {"parts": {k: [] for k in ("rowptr_dst", "rowptr_src", "col_dst", "col_src", "code_dst", "code_src", "ent_rel", "ent")},
-                "pair_cnt": [], "ent_cnt": [], "hop_cnt": [], "max0": 0, "maxk": 0, "rd": [] if with_rd else None, "entries": with_entry_lists}
+                "pair_cnt": [], "ent_cnt": [], "hop_cnt": [], "max0": 0, "maxk": 0, "rd": [] if with_rd else None, "rd_large": rd_large, "entries": with_entry_lists}
 
     def _add_chunk(self, acc, cei, cea, nptr_h, eptr_h):
         """One chunk of graphs: cei [2,Ec] / cea [Ec,K] its K-hop edge list ON THE DEVICE with chunk-local node ids, nptr_h /
@@ -181,7 +190,7 @@ class KHopDataset:
         gc, Nc = nptr_h.shape[0] - 1, int(nptr_h[-1])
         if acc["rd"] is not None:
             from .ops import resistance_distance
-            acc["rd"].append(resistance_distance(nptr_h, eptr_h, cei, dev)[0])
+            acc["rd"].append(resistance_distance(nptr_h, eptr_h, cei, dev, large=acc["rd_large"])[0])
         csr = KHopCSR.build(cei, cea, Nc, nodes_per_tile=1 if with_entry_lists else None)
         acc["max0"], acc["maxk"] = max(acc["max0"], csr.max_code0), max(acc["maxk"], csr.max_codek)
         nptr = torch.from_numpy(np.ascontiguousarray(nptr_h)).to(dev)             # [gc+1] chunk-local node offsets

@@ -164,16 +164,19 @@ def resistance_distance_host(n, edge_index):
     return ((Lp[0, 0] + np.diagonal(Lp)) - Lp[0, :]) - Lp[:, 0]
 
 
-def resistance_distance(data):
+def resistance_distance(data, large="host"):
     """Same contract as the reference's data_utils.resistance_distance (:280-303): sets `data.rd` [num_nodes, 1] float32 from
     `data.edge_index` / `data.num_nodes` and returns `data`.  The feature follows the edge list it is handed - after the K-hop
     transform that is the K-hop edge list, as in the reference's pipeline.  A device `edge_index` takes the batched kernel
-    (ops.resistance_distance, one graph), a host one the float64 route above; `rd` lands where `edge_index` lives."""
+    (ops.resistance_distance, one graph; `large` is passed on: who serves a graph of more than 128 nodes there), a host one the
+    float64 route above; `rd` lands where `edge_index` lives."""
+    if large not in ("host", "device"):
+        raise ValueError(f"unknown large {large!r}")
     edge_index = data.edge_index
     num_nodes = data.num_nodes if getattr(data, "num_nodes", None) is not None else data.x.size(0)
     if edge_index.is_cuda:
         from .ops import resistance_distance as rd_device
-        data.rd = rd_device([0, num_nodes], [0, edge_index.size(1)], edge_index, edge_index.device)[0]
+        data.rd = rd_device([0, num_nodes], [0, edge_index.size(1)], edge_index, edge_index.device, large=large)[0]
     else:
         data.rd = torch.from_numpy(resistance_distance_host(num_nodes, edge_index).astype(np.float32)).unsqueeze(1)
     return data

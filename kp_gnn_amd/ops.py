@@ -2146,14 +2146,38 @@ def _host_i64(a):
     return np.ascontiguousarray(np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.int64)).reshape(-1)
 
 
-def resistance_distance(node_ptr, edge_ptr, edge_index, device):
+def _rd_large_chunks(ids, nodes, slab_bytes, workspace_bytes):
+    """`ids` (graphs of 129 .. RD_LARGE_MAX_NODES nodes, in call order) cut into runs whose slabs - each sized for the run's
+    largest graph - fit `workspace_bytes`; a graph that does not fit alone is a run of its own.  [(ids, max_nodes, bytes)]."""
+    out, i = [], 0
+    while i < ids.size:
+        j, cap = i + 1, int(nodes[ids[i]])
+        while j < ids.size:
+            c = max(cap, int(nodes[ids[j]]))
+            if (j + 1 - i) * slab_bytes(c) > workspace_bytes:
+                break
+            j, cap = j + 1, c
+        out.append((ids[i:j], cap, (j - i) * slab_bytes(cap)))
+        i = j
+    return out
+
+
+def resistance_distance(node_ptr, edge_ptr, edge_index, device, large="host", workspace_bytes=1 << 30):
     """The reference's `rd` node feature (data_utils.py:280-303) of G graphs at once: (rd [N,1] float32 on `device`, status
     [G] int32 on the host).  node_ptr / edge_ptr [G+1]: host offsets of each graph's nodes and edges; edge_index [2,E] int64
     (host or device): ids global within the call, edges grouped by graph.  The graphs are bucketed by size on the host, one
     kpgnn_resistance_distance launch per class (n <= 32: a wavefront per graph; n <= 128: a block per graph), and `status` is
-    read back once.  It tells which graphs the kernel served (0); those it did not - a directed list (1), more than 128
-    nodes (2), a failed pivot (3) - are filled from khop_transform.resistance_distance_host, and an edge endpoint outside
-    its graph (4) raises IndexError before anything else is launched or filled."""
+    read back once.  It tells which graphs the kernel served (0); those it did not - a directed list (1), more nodes than the
+    kernels serve (2), a failed pivot (3) - are filled from khop_transform.resistance_distance_host, and an edge endpoint
+    outside its graph (4) raises IndexError before anything else is launched or filled.
+    large: who serves a graph of more than 128 nodes.  "host": nobody on the device - it gets status 2 from the block-class
+    launch and the float64 host route fills it.  "device": a third class, 128 < n <= 2048, goes to
+    kpgnn_resistance_distance_large (csrc/resistance_large.hip: the matrix in a device workspace, blocked Gauss-Jordan), in
+    runs of graphs whose slabs fit `workspace_bytes` (one graph always runs, whatever it needs), one launch per run on one
+    workspace allocated once per call; status 2 is then n > 2048.  The two are different float64 computations: their float32
+    roundings may differ in the last bit."""
+    if large not in ("host", "device"):
+        raise ValueError(f"unknown large {large!r}")
     node_ptr, edge_ptr = _host_i64(node_ptr), _host_i64(edge_ptr)
     G = node_ptr.shape[0] - 1
     if G < 0 or edge_ptr.shape[0] != G + 1:
@@ -2175,7 +2199,11 @@ def resistance_distance(node_ptr, edge_ptr, edge_index, device):
     st = torch.empty(G, dtype=torch.int32, device=dev)
     nodes = np.diff(node_ptr)
     keep = []
-    for ids in (np.flatnonzero(nodes <= _lib.RD_WAVE_NODES), np.flatnonzero(nodes > _lib.RD_WAVE_NODES)):
+    block_class = nodes > _lib.RD_WAVE_NODES
+    if large == "device":
+        big = np.flatnonzero((nodes > _lib.RD_MAX_NODES) & (nodes <= _lib.RD_LARGE_MAX_NODES))
+        block_class = block_class & ((nodes <= _lib.RD_MAX_NODES) | (nodes > _lib.RD_LARGE_MAX_NODES))
+    for ids in (np.flatnonzero(nodes <= _lib.RD_WAVE_NODES), np.flatnonzero(block_class)):
         if ids.size == 0:
             continue
         ids_d = torch.from_numpy(ids.astype(np.int32)).to(dev)
@@ -2186,6 +2214,20 @@ def resistance_distance(node_ptr, edge_ptr, edge_index, device):
         d.max_nodes = max(1, min(_lib.RD_MAX_NODES, int(nodes[ids].max())))     # (larger graphs get status 2 from the kernel)
         d.out, d.status = out.data_ptr(), st.data_ptr()
         _lib.launch("kpgnn_resistance_distance", dev, ctypes.byref(d))
+    if large == "device" and big.size:
+        slab = lambda cap: int(_lib.load().kpgnn_rd_large_workspace_bytes(cap, 1))  # noqa: E731
+        runs = _rd_large_chunks(big, nodes, slab, int(workspace_bytes))
+        ws = torch.empty(max(r[2] for r in runs), dtype=torch.uint8, device=dev)
+        keep.append(ws)
+        for ids, cap, nbytes in runs:
+            ids_d = torch.from_numpy(ids.astype(np.int32)).to(dev)
+            keep.append(ids_d)
+            d = _lib.RdLargeDesc()
+            d.G, d.n_ids, d.E, d.max_nodes = G, ids.size, E, cap
+            d.node_ptr, d.edge_ptr, d.edge_index, d.graph_ids = nptr.data_ptr(), eptr.data_ptr(), ei.data_ptr(), ids_d.data_ptr()
+            d.out, d.status = out.data_ptr(), st.data_ptr()
+            d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
+            _lib.launch("kpgnn_resistance_distance_large", dev, ctypes.byref(d))
     status = st.cpu()
     del keep
     bad = status.numpy()
