@@ -1591,6 +1591,56 @@ typedef struct kpgnn_collision_desc {
 int64_t kpgnn_collision_workspace_bytes(int64_t N);
 int kpgnn_collision_count(const kpgnn_collision_desc* d, kpgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Labels of the synthetic graph- and node-property dataset (csrc/graph_labels.hip; datasets/GraphPropertyDataset.py
+ * genereate_dataset, datasets/graph_algorithms.py).  For each graph g of n = node_ptr[g+1] - node_ptr[g] <= 64 nodes, with A
+ * the 0/1 adjacency of its edges (duplicates collapse), F = features[node_ptr[g] ..] and s = source[g]:
+ *   node_out[node_ptr[g] + i, 0] = sssp          BFS distance from s to i; 0 for s itself and for an unreachable node
+ *   node_out[.., 1]              = eccentricity  the largest finite distance from i (within its component; 0 when isolated)
+ *   node_out[.., 2]              = laplacian     (float)(deg(i) F[i] - sum_{j in adj(i)} F[j]), in double, ascending j
+ *   graph_out[g, 0] = is_connected    1.0f iff every ordered pair (i, j), i == j included, has a walk of length exactly 2^m,
+ *                                     m = 1 + ceil(log2 n): the reference's repeated squaring, not true connectivity (a
+ *                                     connected bipartite graph answers 0, so does n == 1), as m boolean squarings
+ *   graph_out[g, 1] = diameter        the largest finite distance of the graph (0 when it has no edge)
+ *   graph_out[g, 2] = spectral_radius (float) of the largest eigenvalue of A in double: Householder tridiagonalisation in LDS
+ *                                     and Sturm-count multisection (64 probes a round); exactly 0 when the graph has no edge
+ * status[g] (written for every graph of `graph_ids`; node_out / graph_out are written only where it is 0):
+ *   KPGNN_GL_OK 0          served
+ *   KPGNN_GL_ASYMMETRIC 1  A != A^T: a directed list, the host route's job
+ *   KPGNN_GL_TOO_LARGE 2   n > max_nodes of this launch (the cap of any launch is KPGNN_GL_MAX_NODES: a row is one 64-bit word)
+ *   KPGNN_GL_ENDPOINT 3    an edge endpoint outside [0, n)
+ *   KPGNN_GL_SELF_LOOP 4   an edge (i, i): the reference asserts there is none
+ *   KPGNN_GL_SOURCE 5      source[g] outside [0, n)
+ * (3 wins over 4, 4 over 5, 5 over 1; every range is checked before anything is indexed with it.)  One launch serves the
+ * graphs `graph_ids[0 .. n_ids)`.  max_nodes <= KPGNN_GL_WAVE_NODES: one wavefront per graph, four graphs per block, no block
+ * barrier; above: one block per graph.  The caller buckets its graphs by size and makes one call per class.  No global
+ * atomics, no float atomics, every cross-lane sum in index order: the bits of a graph depend on that graph alone - not on
+ * the edge order, the other graphs of the launch, graph_ids or the size class.  G == 0 or n_ids == 0 return KPGNN_OK without
+ * a launch; n == 0 writes status 0 and a zero graph_out row; ids outside [0, G) are skipped; edges are read from
+ * [edge_ptr[g], edge_ptr[g+1]) clipped to [0, E).  max_nodes < 1 is KPGNN_EINVAL and > 64 KPGNN_ELIMIT, before any device call.
+ * ---------------------------------------------------------------------------------------------- */
+enum { KPGNN_GL_OK = 0, KPGNN_GL_ASYMMETRIC = 1, KPGNN_GL_TOO_LARGE = 2, KPGNN_GL_ENDPOINT = 3, KPGNN_GL_SELF_LOOP = 4,
+       KPGNN_GL_SOURCE = 5 };
+#define KPGNN_GL_MAX_NODES 64
+#define KPGNN_GL_WAVE_NODES 32
+
+typedef struct kpgnn_graph_labels_desc {
+    int32_t G, n_ids;           /* graphs of the call; graphs this launch serves */
+    const int64_t* node_ptr;    /* device [G+1] */
+    const int64_t* edge_ptr;    /* device [G+1] */
+    const int64_t* edge_index;  /* device [2,E] contiguous: LOCAL ids (0 .. n-1 within each graph), edges grouped by graph */
+    int64_t E;                  /* edges of the call (the row length of edge_index) */
+    const int32_t* graph_ids;   /* device [n_ids] */
+    int32_t max_nodes, reserved;/* largest n this launch is sized for, 1 .. KPGNN_GL_MAX_NODES; 0 */
+    const double* features;     /* device [N] */
+    const int32_t* source;      /* device [G]: the local id of each graph's source node */
+    float* node_out;            /* device [N,3]: sssp, eccentricity, laplacian */
+    float* graph_out;           /* device [G,3]: is_connected, diameter, spectral_radius */
+    int32_t* status;            /* device [G] */
+} kpgnn_graph_labels_desc;
+
+int kpgnn_graph_labels(const kpgnn_graph_labels_desc* d, kpgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

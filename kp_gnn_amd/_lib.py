@@ -433,6 +433,17 @@ class CollisionDesc(ctypes.Structure):
 
 COLLISION_MAX_D = 256                                                   # csrc/collisions.hip kMaxD
 
+GL_OK, GL_ASYMMETRIC, GL_TOO_LARGE, GL_ENDPOINT, GL_SELF_LOOP, GL_SOURCE = 0, 1, 2, 3, 4, 5    # include/kpgnn.h KPGNN_GL_*
+GL_MAX_NODES, GL_WAVE_NODES = 64, 32                                    # KPGNN_GL_MAX_NODES, KPGNN_GL_WAVE_NODES
+
+
+class GraphLabelsDesc(ctypes.Structure):
+    _fields_ = [
+        ("G", c_i32), ("n_ids", c_i32), ("node_ptr", c_vp), ("edge_ptr", c_vp), ("edge_index", c_vp), ("E", c_i64),
+        ("graph_ids", c_vp), ("max_nodes", c_i32), ("reserved", c_i32), ("features", c_vp), ("source", c_vp),
+        ("node_out", c_vp), ("graph_out", c_vp), ("status", c_vp),
+    ]
+
 
 class AttnPoolDesc(ctypes.Structure):
     _fields_ = [
@@ -555,6 +566,7 @@ SIGNATURES = {
     "kpgnn_khop_large_fill": (ctypes.c_int, [ctypes.POINTER(KhopDevDesc), c_vp]),
     "kpgnn_collision_workspace_bytes": (c_i64, [c_i64]),
     "kpgnn_collision_count": (ctypes.c_int, [ctypes.POINTER(CollisionDesc), c_vp]),
+    "kpgnn_graph_labels": (ctypes.c_int, [ctypes.POINTER(GraphLabelsDesc), c_vp]),
     "kpgnn_vn_add_pool": (ctypes.c_int, [ctypes.POINTER(VnDesc), c_vp]),
     "kpgnn_dropout_fwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
     "kpgnn_dropout_bwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),

@@ -65,7 +65,7 @@ class KHopDataset:
 
     # ------------------------------------------------------------------------------------------------ construction
     @staticmethod
-    def from_collated(batch, node_ptr, device, chunk_graphs=4096, with_entry_lists=True, with_rd=False, rd_large="host"):
+    def from_collated(batch, node_ptr, device, chunk_graphs=4096, with_entry_lists=True, with_rd=False, rd_large="host", pos=None):
         """`batch`: a HOST KHopBatch holding ALL graphs collated (batch.collate_khop: the reference's pre_transform output in
         PyG's concatenated layout); node_ptr [G+1] its slices.  The CSR is built chunk by chunk on the device.
         with_rd: also compute the resistance-distance node feature (`--use_rd`) per chunk with ops.resistance_distance from the
@@ -74,7 +74,9 @@ class KHopDataset:
         `batch.rd` that is already there is carried as given, whatever with_rd says.
         rd_large: ops.resistance_distance's `large` - who computes that column for a graph of more than 128 nodes: "host" the
         float64 host route, "device" csrc/resistance_large.hip (up to RD_LARGE_MAX_NODES nodes).  Two float64 computations: the
-        float32 rows they give may differ in the last bit, which is why this is not from_graphs' `large`."""
+        float32 rows they give may differ in the last bit, which is why this is not from_graphs' `large`.
+        pos: node targets [N, ...] (the reference's Data.pos of the node-property task, e.g. ops.graph_property_labels' node
+        labels), kept as node_rows["pos"] in the dtype given, so that every collated batch has `.pos`; None: no such rows."""
         if rd_large not in ("host", "device"):
             raise ValueError(f"unknown rd_large {rd_large!r}")
         if batch.edge_index.is_cuda:
@@ -109,7 +111,7 @@ class KHopDataset:
             ds._add_chunk(acc, cei, cea, node_ptr[g0:g1 + 1] - n0, edge_ptr[g0:g1 + 1] - e0)
             del cei, cea
         ds._finish(acc, node_ptr, edge_cnt)
-        ds._attach_rows(batch.x, getattr(batch, "z", None), batch.y, given_rd)
+        ds._attach_rows(batch.x, getattr(batch, "z", None), batch.y, given_rd, pos)
         pea, pca = batch.peripheral_edge_attr, batch.peripheral_configuration_attr
         if pea is not None and pca is not None:
             ds._build_dictionary(pea, pca)
@@ -117,7 +119,7 @@ class KHopDataset:
 
     @staticmethod
     def from_graphs(node_ptr, edge_ptr, edge_index, edge_attr, device, khop_args, x=None, z=None, y=None, chunk_graphs=4096,
-                    with_entry_lists=True, with_rd=False, route="auto", large="auto", rd_large="host"):
+                    with_entry_lists=True, with_rd=False, route="auto", large="auto", rd_large="host", pos=None):
         """The dataset from RAW graphs: node_ptr / edge_ptr [G+1] host offsets, edge_index [2,E] LOCAL ids and edge_attr [E] or
         None (what khop_transform.khop_batch takes), khop_args = (K, max_edge_attr_num, max_hop_num, max_edge_type,
         max_edge_count, max_distance_count, kernel); x / z [N, ...] node and y [G, ...] graph attributes.
@@ -130,7 +132,8 @@ class KHopDataset:
         kernels of csrc/khop_large.hip (up to KHOP_LARGE_MAX_NODES nodes), "host" khop_batch; "auto" is LARGE_AUTO, which
         DESIGN.md 5.21 decides from a measurement.  The dataset is the same bit for bit whichever is chosen.
         rd_large (with_rd, either route): from_collated's keyword of that name, the `large` of the per-chunk
-        ops.resistance_distance."""
+        ops.resistance_distance.
+        pos: from_collated's keyword of that name, the node targets [N, ...] (either route)."""
         if route not in ("auto", "device", "host"):
             raise ValueError(f"unknown route {route!r}")
         if large not in ("auto", "device", "host"):
@@ -141,7 +144,7 @@ class KHopDataset:
         from . import khop_transform as KT
         node_ptr, edge_ptr = np.asarray(node_ptr, dtype=np.int64), np.asarray(edge_ptr, dtype=np.int64)
         as_t = lambda a: a if a is None or torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
-        edge_index, edge_attr, x, z, y = as_t(edge_index), as_t(edge_attr), as_t(x), as_t(z), as_t(y)
+        edge_index, edge_attr, x, z, y, pos = as_t(edge_index), as_t(edge_attr), as_t(x), as_t(z), as_t(y), as_t(pos)
         if route == "host":
             from .batch import KHopBatch
             out = KT.khop_batch(node_ptr, edge_ptr, edge_index.cpu().numpy(), None if edge_attr is None else edge_attr.cpu().numpy(),
@@ -151,7 +154,7 @@ class KHopDataset:
                            peripheral_configuration_attr=out["peripheral_configuration_attr"], batch=out["batch"],
                            num_graphs=node_ptr.shape[0] - 1)
             hb.edge_ptr = out["edge_ptr"].numpy()
-            return KHopDataset.from_collated(hb, node_ptr, device, chunk_graphs, with_entry_lists, with_rd, rd_large)
+            return KHopDataset.from_collated(hb, node_ptr, device, chunk_graphs, with_entry_lists, with_rd, rd_large, pos=pos)
         from .ops import khop_transform
         ds = KHopDataset()
         G = node_ptr.shape[0] - 1
@@ -171,7 +174,7 @@ class KHopDataset:
                 pcas.append(out["peripheral_configuration_attr"])
             del out
         ds._finish(acc, node_ptr, np.concatenate(edge_cnt) if edge_cnt else np.zeros(0, np.int64))
-        ds._attach_rows(x, z, y, None)
+        ds._attach_rows(x, z, y, None, pos)
         if peas:
             ds._build_dictionary(torch.cat(peas), torch.cat(pcas))
         return ds
@@ -243,8 +246,8 @@ class KHopDataset:
         self.Nd = int(node_ptr[-1])
         self._rd_parts = acc["rd"]
 
-    def _attach_rows(self, x, z, y, given_rd):
-        """Node / graph attributes; `given_rd` wins over the column _add_chunk computed."""
+    def _attach_rows(self, x, z, y, given_rd, pos=None):
+        """Node / graph attributes; `given_rd` wins over the column _add_chunk computed; `pos`: node targets [N, ...]."""
         dev = self.device
         rd_parts, self._rd_parts = self._rd_parts, None
         if x is not None:
@@ -258,6 +261,11 @@ class KHopDataset:
             self.node_rows["rd"] = given_rd.to(device=dev, dtype=torch.float32).reshape(self.Nd, 1).contiguous()
         elif rd_parts is not None:
             self.node_rows["rd"] = torch.cat(rd_parts) if rd_parts else torch.zeros((0, 1), dtype=torch.float32, device=dev)
+        if pos is not None:
+            pos = torch.as_tensor(pos)
+            if pos.dim() < 1 or pos.shape[0] != self.Nd:
+                raise ValueError(f"pos has {pos.shape[0]} rows for {self.Nd} nodes")
+            self.node_rows["pos"] = pos.to(dev).contiguous()
         if y is not None:
             self.graph_rows["y"] = y.to(dev).contiguous()
 

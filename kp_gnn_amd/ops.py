@@ -2248,6 +2248,95 @@ def resistance_distance(node_ptr, edge_ptr, edge_index, device, large="host", wo
     return out, status
 
 
+# ------------------------------------------------------------------------------------------------ graph-property labels
+GRAPH_LABELS_AUTO = "device"     # graph_property_labels(route="auto"): DESIGN.md 5.24 has the measurement behind it
+
+
+def graph_labels_launch(G, nptr, eptr, ei, E, feat, src, ids, max_nodes, node_out, graph_out, status):
+    """One kpgnn_graph_labels launch over device tensors: the graphs `ids` (int32) of a call of G graphs, sized for max_nodes."""
+    d = _lib.GraphLabelsDesc()
+    d.G, d.n_ids, d.E, d.max_nodes = G, ids.numel(), E, max_nodes
+    d.node_ptr, d.edge_ptr, d.edge_index, d.graph_ids = nptr.data_ptr(), eptr.data_ptr(), ei.data_ptr(), ids.data_ptr()
+    d.features, d.source = feat.data_ptr(), src.data_ptr()
+    d.node_out, d.graph_out, d.status = node_out.data_ptr(), graph_out.data_ptr(), status.data_ptr()
+    _lib.launch("kpgnn_graph_labels", node_out.device, ctypes.byref(d))
+
+
+def graph_property_labels(node_ptr, edge_ptr, edge_index, features, source, device, route="auto"):
+    """The labels of the reference's graph- and node-property dataset (datasets/GraphPropertyDataset.py genereate_dataset) of G
+    raw graphs at once: (node_labels [N,3] float32: sssp | eccentricity | laplacian features, graph_labels [G,3] float32:
+    is_connected | diameter | spectral_radius), both on `device`.  node_ptr / edge_ptr [G+1]: host offsets; edge_index [2,E]
+    int64 LOCAL ids, edges grouped by graph (host or device); features [N] float32 or float64 (widened to double, which is
+    exact); source [G] the local id of each graph's source node.
+    route "device": the graphs are bucketed by size on the host, one kpgnn_graph_labels launch per class (n <= 32: a
+    wavefront per graph; n <= 64: a block per graph), and `status` is read back once.  Graphs the kernel did not serve - a
+    directed list (1), more than 64 nodes (2) - are filled from graph_property.labels_host_f64 inside the same call; an edge
+    endpoint outside its graph (3), a self loop (4) and a source outside its graph (5) raise ValueError naming the first such
+    graph.  route "host": graph_property.graph_property_labels_host, moved to the device.  "auto" is GRAPH_LABELS_AUTO.  The
+    integer labels are the same whichever route served a graph; the two float64 computations of the spectral radius and of
+    the laplacian column may differ in the last float32 bit."""
+    if route not in ("auto", "device", "host"):
+        raise ValueError(f"unknown route {route!r}")
+    from . import graph_property as GP
+    route = GRAPH_LABELS_AUTO if route == "auto" else route
+    dev = torch.device(device)
+    if route == "host":
+        return GP.graph_property_labels_host(node_ptr, edge_ptr, edge_index, features, source, dev)
+    if dev.type != "cuda":
+        raise _lib.KpgnnError("ops.graph_property_labels(route='device') needs a GPU device: graph_property_labels_host is the host route")
+    node_ptr, edge_ptr, src_h = _host_i64(node_ptr), _host_i64(edge_ptr), _host_i64(source)
+    G = node_ptr.shape[0] - 1
+    if G < 0 or edge_ptr.shape[0] != G + 1 or src_h.shape[0] != G:
+        raise ValueError("node_ptr and edge_ptr must have G + 1 entries and source G")
+    if node_ptr[0] != 0 or edge_ptr[0] != 0 or bool((np.diff(node_ptr) < 0).any()) or bool((np.diff(edge_ptr) < 0).any()):
+        raise ValueError("node_ptr / edge_ptr must start at 0 and not decrease")
+    N, E = int(node_ptr[-1]), int(edge_ptr[-1])
+    if not torch.is_tensor(edge_index):
+        edge_index = torch.from_numpy(np.ascontiguousarray(np.asarray(edge_index, dtype=np.int64)))
+    edge_index = edge_index.reshape(2, -1)
+    if edge_index.shape[1] != E:
+        raise ValueError("edge_index does not match edge_ptr")
+    if not torch.is_tensor(features):
+        features = torch.from_numpy(np.ascontiguousarray(features))
+    if features.dtype not in (torch.float32, torch.float64) or features.numel() != N:
+        raise ValueError("features must be [N] float32 or float64")
+    node_out = torch.zeros((N, 3), dtype=torch.float32, device=dev)
+    graph_out = torch.zeros((G, 3), dtype=torch.float32, device=dev)
+    if G == 0:
+        return node_out, graph_out
+    ei = edge_index.to(device=dev, dtype=torch.int64).contiguous()
+    feat = features.reshape(-1).to(device=dev, dtype=torch.float64).contiguous()
+    src = torch.from_numpy(np.clip(src_h, -1, 1 << 30).astype(np.int32)).to(dev)      # (any value outside [0, n) is status 5)
+    nptr, eptr = torch.from_numpy(node_ptr).to(dev), torch.from_numpy(edge_ptr).to(dev)
+    st = torch.empty(G, dtype=torch.int32, device=dev)
+    nodes = np.diff(node_ptr)
+    keep = []
+    for ids in (np.flatnonzero(nodes <= _lib.GL_WAVE_NODES), np.flatnonzero(nodes > _lib.GL_WAVE_NODES)):
+        if ids.size == 0:
+            continue
+        ids_d = torch.from_numpy(ids.astype(np.int32)).to(dev)
+        keep.append(ids_d)
+        cap = max(1, min(_lib.GL_MAX_NODES, int(nodes[ids].max())))         # (larger graphs get status 2 from the kernel)
+        graph_labels_launch(G, nptr, eptr, ei, E, feat, src, ids_d, cap, node_out, graph_out, st)
+    bad = st.cpu().numpy()
+    del keep
+    refused = np.flatnonzero(bad >= _lib.GL_ENDPOINT)
+    if refused.size:
+        g = int(refused[0])
+        what = {_lib.GL_ENDPOINT: f"an edge endpoint lies outside its nodes [0, {int(nodes[g])})",
+                _lib.GL_SELF_LOOP: "a self loop (the labels are defined for graphs without one)",
+                _lib.GL_SOURCE: f"source {int(src_h[g])} lies outside its nodes [0, {int(nodes[g])})"}[int(bad[g])]
+        raise ValueError(f"graph {g}: {what}")
+    todo = np.flatnonzero(bad != 0)
+    if todo.size:
+        node_h, graph_h = GP.labels_host_f64(node_ptr, edge_ptr, edge_index, features, src_h, graphs=todo)
+        rows = torch.from_numpy(np.concatenate([np.arange(node_ptr[g], node_ptr[g + 1]) for g in todo])).to(dev)
+        node_out[rows] = torch.from_numpy(node_h[rows.cpu().numpy()].astype(np.float32)).to(dev)
+        gi = torch.from_numpy(todo).to(dev)
+        graph_out[gi] = torch.from_numpy(graph_h[todo].astype(np.float32)).to(dev)
+    return node_out, graph_out
+
+
 # ------------------------------------------------------------------------------------------------ the K-hop pre-transform
 def khop_transform(node_ptr, edge_ptr, edge_index, edge_attr, K, max_edge_attr_num, max_hop_num, max_edge_type,
                    max_edge_count, max_distance_count, kernel, device, large="host"):
