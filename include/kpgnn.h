@@ -1641,6 +1641,64 @@ typedef struct kpgnn_graph_labels_desc {
 
 int kpgnn_graph_labels(const kpgnn_graph_labels_desc* d, kpgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Labels of the synthetic substructure-counting dataset (csrc/count_labels.hip; datasets/GraphCountDataset.py process).  For
+ * each graph g of n = node_ptr[g+1] - node_ptr[g] nodes, with A the symmetric 0/1 adjacency of its edges (duplicates
+ * collapse), d_i the degree of node i, c_ij = popcount(row_i & row_j) = (A^2)_ij and T_i = sum_{j in N(i)} c_ij = (A^3)_ii:
+ *   out[g, 0] = tri     trace(A^3) / 6                                  = (sum_i T_i) / 6
+ *   out[g, 1] = tailed  sum_i (A^3)_ii / 2 * (d_i - 2)                  = sum_i (T_i / 2) (d_i - 2)
+ *   out[g, 2] = star    sum_i C(d_i, 3)                                 = sum_i d_i (d_i - 1) (d_i - 2) / 6
+ *   out[g, 3] = cyc4    (trace(A^4) + trace(A^2) - 2 sum(A^2)) / 8      = (sum_ij c_ij^2 + sum_i d_i - 2 sum_i d_i^2) / 8,
+ *                                                                         over all ordered pairs, c_ii = d_i included
+ *   out[g, 4] = cus     sum(A diag(exp(-rowsum(A^2))) A)                = sum_k d_k^2 exp(-s_k), s_k = sum_{j in N(k)} d_j
+ * The first four are sums of 64-bit integers (every division is exact; at 2048 nodes every intermediate stays below 2^53)
+ * converted to double once.  cus is a double sum taken by ONE lane in ascending k, one exp and one product per node, with
+ * floating-point contraction off.
+ * status[g] (written for every graph of `graph_ids`; out[g] is written only where it is 0):
+ *   KPGNN_CL_OK 0          served
+ *   KPGNN_CL_ASYMMETRIC 1  A != A^T: a directed list, the host route's job
+ *   KPGNN_CL_SELF_LOOP 2   an edge (i, i): the host route's job too (the reference's expressions apply literally)
+ *   KPGNN_CL_TOO_LARGE 3   n > max_nodes of this launch (the cap of any launch is KPGNN_CL_MAX_NODES)
+ *   KPGNN_CL_ENDPOINT 4    an edge endpoint outside [0, n), or node_ptr decreasing at g
+ * (3 is decided before the edges are read; then 4 wins over 2 and 2 over 1; every range is checked before anything is indexed
+ * with it.)  One launch serves the graphs `graph_ids[0 .. n_ids)` and is sized by max_nodes:
+ *   max_nodes <= KPGNN_CL_WAVE_NODES  one wavefront per graph, four graphs per 256-thread block, no block barrier; a row of
+ *                                     the adjacency is ONE 64-bit word in LDS, set by LDS atomic OR
+ *   max_nodes <= KPGNN_CL_WORD_NODES  one 256-thread block per graph, the same one-word rows
+ *   max_nodes <= KPGNN_CL_MAX_NODES   one 1024-thread block per graph; the rows are ceil(n / 64) words in the graph's slab of
+ *                                     `workspace` (slab s, of kpgnn_count_labels_workspace_bytes(max_nodes) bytes, belongs to
+ *                                     graph_ids[s]); the kernel zeroes its slab and sets the bits by 64-bit integer atomic OR;
+ *                                     workspace_bytes >= n_ids * kpgnn_count_labels_workspace_bytes(max_nodes), 8-byte aligned.
+ *                                     A smaller graph may be served by a larger class; the two smaller classes ignore workspace.
+ * The caller buckets its graphs by size and makes one call per class.  No float atomics; no global atomics but that OR; the
+ * bits of a graph depend on that graph alone - not on the edge order, duplicated edges, the size class, graph_ids or the other
+ * graphs of the launch.  G == 0 or n_ids == 0 return KPGNN_OK without a launch; n == 0 writes status 0 and five zeros; ids
+ * outside [0, G) are skipped; edges are read from [edge_ptr[g], edge_ptr[g+1]) clipped to [0, E).  max_nodes < 1 is
+ * KPGNN_EINVAL and > KPGNN_CL_MAX_NODES KPGNN_ELIMIT, before any device call.
+ * ---------------------------------------------------------------------------------------------- */
+enum { KPGNN_CL_OK = 0, KPGNN_CL_ASYMMETRIC = 1, KPGNN_CL_SELF_LOOP = 2, KPGNN_CL_TOO_LARGE = 3, KPGNN_CL_ENDPOINT = 4 };
+#define KPGNN_CL_WAVE_NODES 32
+#define KPGNN_CL_WORD_NODES 64
+#define KPGNN_CL_MAX_NODES 2048
+
+typedef struct kpgnn_count_labels_desc {
+    int32_t G, n_ids;           /* graphs of the call; graphs this launch serves */
+    const int64_t* node_ptr;    /* device [G+1] */
+    const int64_t* edge_ptr;    /* device [G+1] */
+    const int64_t* edge_index;  /* device [2,E] contiguous: LOCAL ids (0 .. n-1 within each graph), edges grouped by graph */
+    int64_t E;                  /* edges of the call (the row length of edge_index) */
+    const int32_t* graph_ids;   /* device [n_ids] */
+    int32_t max_nodes, reserved;/* largest n this launch is sized for, 1 .. KPGNN_CL_MAX_NODES; 0 */
+    double* out;                /* device [G,5]: tri, tailed, star, cyc4, cus */
+    int32_t* status;            /* device [G] */
+    void* workspace; size_t workspace_bytes;       /* device; needed only when max_nodes > KPGNN_CL_WORD_NODES */
+} kpgnn_count_labels_desc;
+
+/* Bytes of ONE graph's slab in a launch sized for max_nodes: 0 up to KPGNN_CL_WORD_NODES (the rows live in LDS), else
+ * max_nodes * ceil(max_nodes / 64) * 8.  Never decreases with max_nodes; no device call. */
+size_t kpgnn_count_labels_workspace_bytes(int max_nodes);
+int kpgnn_count_labels(const kpgnn_count_labels_desc* d, kpgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

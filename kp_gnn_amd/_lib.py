@@ -445,6 +445,14 @@ class GraphLabelsDesc(ctypes.Structure):
     ]
 
 
+CL_OK, CL_ASYMMETRIC, CL_SELF_LOOP, CL_TOO_LARGE, CL_ENDPOINT = 0, 1, 2, 3, 4    # include/kpgnn.h KPGNN_CL_*
+CL_WAVE_NODES, CL_WORD_NODES, CL_MAX_NODES = 32, 64, 2048               # KPGNN_CL_WAVE_NODES, _WORD_NODES, _MAX_NODES
+
+
+class CountLabelsDesc(ctypes.Structure):
+    _fields_ = RdDesc._fields_ + [("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t)]     # (`out` is double [G,5] here)
+
+
 class AttnPoolDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i64), ("G", c_i32), ("D", c_i32),
@@ -567,6 +575,8 @@ SIGNATURES = {
     "kpgnn_collision_workspace_bytes": (c_i64, [c_i64]),
     "kpgnn_collision_count": (ctypes.c_int, [ctypes.POINTER(CollisionDesc), c_vp]),
     "kpgnn_graph_labels": (ctypes.c_int, [ctypes.POINTER(GraphLabelsDesc), c_vp]),
+    "kpgnn_count_labels_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "kpgnn_count_labels": (ctypes.c_int, [ctypes.POINTER(CountLabelsDesc), c_vp]),
     "kpgnn_vn_add_pool": (ctypes.c_int, [ctypes.POINTER(VnDesc), c_vp]),
     "kpgnn_dropout_fwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
     "kpgnn_dropout_bwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),

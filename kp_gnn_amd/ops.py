@@ -2337,6 +2337,96 @@ def graph_property_labels(node_ptr, edge_ptr, edge_index, features, source, devi
     return node_out, graph_out
 
 
+# ------------------------------------------------------------------------------------------------ substructure-count labels
+COUNT_LABELS_AUTO = "device"      # count_labels(route="auto"): DESIGN.md 5.25 has the measurement behind it
+
+
+def count_labels_launch(G, nptr, eptr, ei, E, ids, max_nodes, out, status, workspace=None, workspace_bytes=0):
+    """One kpgnn_count_labels launch over device tensors: the graphs `ids` (int32) of a call of G graphs, sized for max_nodes
+    (which picks the size class); `workspace` (uint8) holds a slab per id when max_nodes > CL_WORD_NODES."""
+    d = _lib.CountLabelsDesc()
+    d.G, d.n_ids, d.E, d.max_nodes = G, ids.numel(), E, max_nodes
+    d.node_ptr, d.edge_ptr, d.edge_index, d.graph_ids = nptr.data_ptr(), eptr.data_ptr(), ei.data_ptr(), ids.data_ptr()
+    d.out, d.status = out.data_ptr(), status.data_ptr()
+    d.workspace, d.workspace_bytes = (workspace.data_ptr() if workspace is not None else None), int(workspace_bytes)
+    _lib.launch("kpgnn_count_labels", out.device, ctypes.byref(d))
+
+
+def count_labels(node_ptr, edge_ptr, edge_index, device, route="auto", workspace_bytes=1 << 28):
+    """The labels of the reference's substructure-counting dataset (datasets/GraphCountDataset.py process) of G raw graphs at
+    once: y [G,5] float64 on `device`, tri | tailed | star | cyc4 | cus.  node_ptr / edge_ptr [G+1]: host offsets; edge_index
+    [2,E] int64 LOCAL ids, edges grouped by graph (host or device).
+    route "device": the graphs are bucketed by size on the host, one kpgnn_count_labels launch per class (n <= 32: a wavefront
+    per graph; n <= 64: a block per graph; n <= 2048: a block per graph on a slab of a device workspace, in runs of graphs
+    whose slabs fit `workspace_bytes` - one graph always runs - on one workspace allocated once per call), and `status` is
+    read back once.  Graphs the kernel did not serve - a directed list (1), a self loop (2), more than 2048 nodes (3) - are
+    filled from graph_count.count_labels_host_f64 inside the same call; an edge endpoint outside its graph (4) raises
+    ValueError naming the first such graph.  route "host": graph_count.count_labels_host, moved to the device.  "auto" is
+    COUNT_LABELS_AUTO.  The four integer labels are the same whichever route served a graph; the two float64 sums of cus may
+    differ in their last bits."""
+    if route not in ("auto", "device", "host"):
+        raise ValueError(f"unknown route {route!r}")
+    from . import graph_count as GCN
+    route = COUNT_LABELS_AUTO if route == "auto" else route
+    dev = torch.device(device)
+    if route == "host":
+        return GCN.count_labels_host(node_ptr, edge_ptr, edge_index, dev)
+    if dev.type != "cuda":
+        raise _lib.KpgnnError("ops.count_labels(route='device') needs a GPU device: graph_count.count_labels_host is the host route")
+    node_ptr, edge_ptr = _host_i64(node_ptr), _host_i64(edge_ptr)
+    G = node_ptr.shape[0] - 1
+    if G < 0 or edge_ptr.shape[0] != G + 1:
+        raise ValueError("node_ptr and edge_ptr must both have G + 1 entries")
+    if node_ptr[0] != 0 or edge_ptr[0] != 0 or bool((np.diff(node_ptr) < 0).any()) or bool((np.diff(edge_ptr) < 0).any()):
+        raise ValueError("node_ptr / edge_ptr must start at 0 and not decrease")
+    E = int(edge_ptr[-1])
+    if not torch.is_tensor(edge_index):
+        edge_index = torch.from_numpy(np.ascontiguousarray(np.asarray(edge_index, dtype=np.int64)))
+    edge_index = edge_index.reshape(2, -1)
+    if edge_index.shape[1] != E:
+        raise ValueError("edge_index does not match edge_ptr")
+    out = torch.zeros((G, 5), dtype=torch.float64, device=dev)
+    if G == 0:
+        return out
+    ei = edge_index.to(device=dev, dtype=torch.int64).contiguous()
+    nptr, eptr = torch.from_numpy(node_ptr).to(dev), torch.from_numpy(edge_ptr).to(dev)
+    nodes = np.diff(node_ptr)
+    # (no launch for a graph above the cap: its status is set here; -1 marks a graph no launch wrote, which is an error below)
+    st = torch.from_numpy(np.where(nodes > _lib.CL_MAX_NODES, _lib.CL_TOO_LARGE, -1).astype(np.int32)).to(dev)
+    keep = []
+    word = nodes <= _lib.CL_WORD_NODES
+    for ids, cap in ((np.flatnonzero(nodes <= _lib.CL_WAVE_NODES), _lib.CL_WAVE_NODES),
+                     (np.flatnonzero(word & (nodes > _lib.CL_WAVE_NODES)), _lib.CL_WORD_NODES)):
+        if ids.size == 0:
+            continue
+        ids_d = torch.from_numpy(ids.astype(np.int32)).to(dev)
+        keep.append(ids_d)
+        count_labels_launch(G, nptr, eptr, ei, E, ids_d, cap, out, st)
+    big = np.flatnonzero(~word & (nodes <= _lib.CL_MAX_NODES))
+    if big.size:
+        slab = lambda cap: int(_lib.load().kpgnn_count_labels_workspace_bytes(cap))  # noqa: E731
+        runs = _rd_large_chunks(big, nodes, slab, int(workspace_bytes))
+        ws = torch.empty(max(r[2] for r in runs), dtype=torch.uint8, device=dev)
+        keep.append(ws)
+        for ids, cap, nbytes in runs:
+            ids_d = torch.from_numpy(ids.astype(np.int32)).to(dev)
+            keep.append(ids_d)
+            count_labels_launch(G, nptr, eptr, ei, E, ids_d, cap, out, st, ws, nbytes)
+    bad = st.cpu().numpy()
+    del keep
+    refused = np.flatnonzero(bad == _lib.CL_ENDPOINT)
+    if refused.size:
+        g = int(refused[0])
+        raise ValueError(f"graph {g}: an edge endpoint lies outside its nodes [0, {int(nodes[g])})")
+    if bool((bad < 0).any()):
+        raise _lib.KpgnnError(f"kpgnn_count_labels left graph {int(np.flatnonzero(bad < 0)[0])} without a status")
+    todo = np.flatnonzero(bad != _lib.CL_OK)
+    if todo.size:
+        y = GCN.count_labels_host_f64(node_ptr, edge_ptr, edge_index, graphs=todo)
+        out[torch.from_numpy(todo).to(dev)] = torch.from_numpy(y[todo]).to(dev)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ the K-hop pre-transform
 def khop_transform(node_ptr, edge_ptr, edge_index, edge_attr, K, max_edge_attr_num, max_hop_num, max_edge_type,
                    max_edge_count, max_distance_count, kernel, device, large="host"):
