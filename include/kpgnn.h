@@ -318,6 +318,19 @@ int kpgnn_khop_pull_gather(const kpgnn_pull_gather_desc* d, kpgnn_stream_t strea
  * before and after its call. */
 int64_t kpgnn_agg_lds_launch_count(void);
 
+/* The same for every kernel behind kpgnn_aggregate_fwd / kpgnn_aggregate_bwd: which of them served a call depends on shape
+ * thresholds only (narrow rows, small batches, graph boundaries given) and leaves no other trace.  fwd[r] / bwd[r] receive how
+ * many calls of this process were served by route r (either array may be NULL); host-side relaxed atomics, test support only.
+ * fwd[KPGNN_AGG_ROUTE_LDS] is what kpgnn_agg_lds_launch_count returns; the backward has no LDS-staged kernel, so
+ * bwd[KPGNN_AGG_ROUTE_LDS] stays 0.  kpgnn_khop_pull_gather is not counted. */
+enum {
+    KPGNN_AGG_ROUTE_SUBGROUP = 0,   /* agg_fwd_kernel / agg_bwd_kernel: a sub-group of lanes per node */
+    KPGNN_AGG_ROUTE_NARROW = 1,     /* agg_narrow_kernel: a thread per output element (D <= 32) */
+    KPGNN_AGG_ROUTE_SMALL = 2,      /* agg_fwd_small_kernel / agg_bwd_small_kernel: a block per node (N <= 4096) */
+    KPGNN_AGG_ROUTE_LDS = 3         /* agg_lds_fwd_kernel: a graph's hop slab staged in LDS */
+};
+int kpgnn_agg_launch_counts(int64_t fwd[4], int64_t bwd[4]);
+
 /* Backward of the aggregation w.r.t. x and the two edge-code tables, given g = dL/dS [N,K,D]
  * (the caller applies the activation derivative; for GCN g already includes relu').
  *   gx[j,k,:]      = sum over pairs a of segment (j,k) of the BY-SOURCE csr of w_a * g[col[a],k,:]  (+ self terms)

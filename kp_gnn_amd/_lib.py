@@ -9,6 +9,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "libkpgnn_hip.so")
 
 MODE_GIN, MODE_GINPLUS, MODE_GCN, MODE_SUM = 0, 1, 2, 3
+ROUTE_SUBGROUP, ROUTE_NARROW, ROUTE_SMALL, ROUTE_LDS = 0, 1, 2, 3      # include/kpgnn.h KPGNN_AGG_ROUTE_*
 
 c_i32, c_i64, c_f32p, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p
 
@@ -520,6 +521,7 @@ SIGNATURES = {
     "kpgnn_aggregate_fwd": (ctypes.c_int, [ctypes.POINTER(AggFwdDesc), c_vp]),
     "kpgnn_khop_pull_gather": (ctypes.c_int, [ctypes.POINTER(PullGatherDesc), c_vp]),
     "kpgnn_agg_lds_launch_count": (c_i64, []),
+    "kpgnn_agg_launch_counts": (ctypes.c_int, [ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "kpgnn_aggregate_bwd": (ctypes.c_int, [ctypes.POINTER(AggBwdDesc), c_vp]),
     "kpgnn_table_grad_workspace_bytes": (ctypes.c_size_t, [c_i32] * 7),
     "kpgnn_table_grad": (ctypes.c_int, [ctypes.POINTER(TableGradDesc), c_vp]),
@@ -646,6 +648,13 @@ def load(path=None):
         raise KpgnnError("libkpgnn_hip.so ABI version mismatch")
     _lib = lib
     return lib
+
+
+def agg_launch_counts():
+    """(fwd, bwd): per KPGNN_AGG_ROUTE_* how many kpgnn_aggregate_fwd / _bwd calls of this process each kernel served"""
+    fwd, bwd = (c_i64 * 4)(), (c_i64 * 4)()
+    check(load().kpgnn_agg_launch_counts(fwd, bwd), "kpgnn_agg_launch_counts")
+    return list(fwd), list(bwd)
 
 
 def check(rc, what):

@@ -726,6 +726,14 @@ using namespace kpgnn;
 
 extern "C" int64_t kpgnn_agg_lds_launch_count(void) { return agg_lds_launch_count(); }
 
+extern "C" int kpgnn_agg_launch_counts(int64_t fwd[4], int64_t bwd[4]) {
+    for (int r = 0; r < 4; ++r) {
+        if (fwd) fwd[r] = agg_route_count(0, r);
+        if (bwd) bwd[r] = agg_route_count(1, r);
+    }
+    return KPGNN_OK;
+}
+
 extern "C" int kpgnn_aggregate_fwd(const kpgnn_agg_fwd_desc* d, kpgnn_stream_t stream) {
     KPGNN_REQUIRE(d != nullptr, "aggregate_fwd: NULL descriptor");
     KPGNN_REQUIRE(d->N >= 0 && d->K >= 1 && d->D >= 1 && d->K_csr >= d->K, "aggregate_fwd: bad N=%d K=%d D=%d K_csr=%d",
@@ -819,8 +827,10 @@ extern "C" int kpgnn_aggregate_fwd(const kpgnn_agg_fwd_desc* d, kpgnn_stream_t s
             if (rc != KPGNN_OK) return rc;
         }
     }
-    return dispatch_row_shape<64>(vec, g, "aggregate_fwd",
-                                  [&](auto VV, auto G) { return launch_fwd_mode<VV.value, G.value>(p, tab, lds, s); });
+    const int rc = dispatch_row_shape<64>(vec, g, "aggregate_fwd",
+                                          [&](auto VV, auto G) { return launch_fwd_mode<VV.value, G.value>(p, tab, lds, s); });
+    if (rc == KPGNN_OK) agg_route_bump(0, KPGNN_AGG_ROUTE_SUBGROUP);
+    return rc;
 }
 
 extern "C" int kpgnn_khop_pull_gather(const kpgnn_pull_gather_desc* d, kpgnn_stream_t stream) {
@@ -917,6 +927,8 @@ extern "C" int kpgnn_aggregate_bwd(const kpgnn_agg_bwd_desc* d, kpgnn_stream_t s
     const int lanes = (d->D + vec - 1) / vec;
     if (lanes > 64) return fail(KPGNN_ELIMIT, "aggregate_bwd: D=%d with %d-wide access needs %d lanes > 64", d->D, vec, lanes);
     hipStream_t s = (hipStream_t)stream;
-    return dispatch_row_shape<64>(vec, row_lanes(d->D, vec), "aggregate_bwd",
-                                  [&](auto VV, auto G) { return launch_bwd_mode<VV.value, G.value>(p, tab, lds, s); });
+    const int rc = dispatch_row_shape<64>(vec, row_lanes(d->D, vec), "aggregate_bwd",
+                                          [&](auto VV, auto G) { return launch_bwd_mode<VV.value, G.value>(p, tab, lds, s); });
+    if (rc == KPGNN_OK) agg_route_bump(1, KPGNN_AGG_ROUTE_SUBGROUP);
+    return rc;
 }

@@ -87,11 +87,15 @@ agg_lds_fwd_kernel(const LdsAggParams p) {
     }
 }
 
-std::atomic<int64_t> g_lds_launches{0};     // host side, per process: launches of agg_lds_fwd_kernel (kpgnn_agg_lds_launch_count)
+// host side, per process: launches by direction and KPGNN_AGG_ROUTE_* (kpgnn_agg_launch_counts); [0][LDS] are the launches of
+// agg_lds_fwd_kernel (kpgnn_agg_lds_launch_count)
+std::atomic<int64_t> g_route_launches[2][4];
 
 }  // namespace
 
-int64_t agg_lds_launch_count() { return g_lds_launches.load(std::memory_order_relaxed); }
+void agg_route_bump(int bwd, int route) { g_route_launches[bwd ? 1 : 0][route & 3].fetch_add(1, std::memory_order_relaxed); }
+int64_t agg_route_count(int bwd, int route) { return g_route_launches[bwd ? 1 : 0][route & 3].load(std::memory_order_relaxed); }
+int64_t agg_lds_launch_count() { return agg_route_count(0, KPGNN_AGG_ROUTE_LDS); }
 
 // Returns KPGNN_OK with *handled = true when the launch was done here; *handled = false leaves it to the other kernels.
 int agg_lds_fwd(const kpgnn_agg_fwd_desc* d, hipStream_t s, bool* handled) {
@@ -129,7 +133,7 @@ int agg_lds_fwd(const kpgnn_agg_fwd_desc* d, hipStream_t s, bool* handled) {
     }
 #undef KP_LDSAGG
     KPGNN_LAUNCH_CHECK("agg_lds_fwd_kernel");
-    g_lds_launches.fetch_add(1, std::memory_order_relaxed);
+    agg_route_bump(0, KPGNN_AGG_ROUTE_LDS);
     *handled = true;
     return KPGNN_OK;
 }

@@ -7,7 +7,10 @@
 // segment (i, k): all K hops of a node advance in parallel across lanes, the dependency chain is three loads deep
 // (row pointer -> pair -> row) whatever K is, consecutive lanes read consecutive floats of the same 52-byte row (one
 // request) and the same pair-list entry (a broadcast).  Pairs are added in list order, as the reference's
-// index_add_ over edges does (KPGIN.py:96-105) - results do not depend on the kernel choice.
+// index_add_ over edges does (KPGIN.py:96-105): the forward's results do not depend on the kernel choice (bit for bit
+// those of the sub-group kernels).  The backward's do where a self term (GIN) or an accumulate_mask bit is added: here
+// both follow the segment's last pair, agg_bwd_kernel's chunked loop adds them behind the hop's first PF pairs, where
+// they arrive - the same sums in another order, equal to rounding and not bit for bit.
 // Measured (round 2): it wins where a launch is latency-bound - 3-regular n = 1280, 582 pairs per node, batch 1: 31 us
 // against 239; QM9-shaped batch 128: 11 us against 33 - and loses where the sub-group kernels' prefetch across hops keeps
 // more rows in flight per wave: ZINC batch 2048 (N = 47k, D = 13) 64 us against 47, regular batch 100 1.34 ms against 0.95.
@@ -131,7 +134,9 @@ int agg_narrow_fwd(const kpgnn_agg_fwd_desc* d, hipStream_t s, bool* handled) {
     p.xbias = d->xbias; p.eps = d->eps; p.self_term = d->mode == KPGNN_MODE_GIN ? 1 : 0;
     p.out = d->out; p.o_sn = d->o_sn; p.o_sk = d->o_sk; p.pre = d->pre; p.acc_mask = 0;
     *handled = true;
-    return agg_narrow_launch(p, s);
+    const int rc = agg_narrow_launch(p, s);
+    if (rc == KPGNN_OK) agg_route_bump(0, KPGNN_AGG_ROUTE_NARROW);
+    return rc;
 }
 
 int agg_narrow_bwd(const kpgnn_agg_bwd_desc* d, hipStream_t s, bool* handled) {
@@ -150,7 +155,9 @@ int agg_narrow_bwd(const kpgnn_agg_bwd_desc* d, hipStream_t s, bool* handled) {
     p.xbias = nullptr; p.eps = d->eps; p.self_term = d->mode == KPGNN_MODE_GIN ? 1 : 0;
     p.out = d->gx; p.o_sn = d->gx_sn; p.o_sk = d->gx_sk; p.pre = nullptr; p.acc_mask = d->accumulate_mask;
     *handled = true;
-    return agg_narrow_launch(p, s);
+    const int rc = agg_narrow_launch(p, s);
+    if (rc == KPGNN_OK) agg_route_bump(1, KPGNN_AGG_ROUTE_NARROW);
+    return rc;
 }
 
 }  // namespace kpgnn

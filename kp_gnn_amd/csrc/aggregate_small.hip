@@ -7,7 +7,9 @@
 // 12 us backward at N = 1495, K = 8, D = 104.  Here the K hops of a node are gathered by K units of one block at the same
 // time (lane = four feature columns, as there), so the chain is three loads deep - row pointers -> pair list -> rows -
 // whatever K is; the hops meet in LDS for the fused geometric combine.  Same order of every sum as the sub-group kernels
-// (pairs in list order, hops in order); theta * v is rounded before the hop sum here, fused there (1 ulp).
+// (pairs in list order, hops in order): S and gx are theirs bit for bit.  Two exceptions, equal to rounding only: theta * v
+// is rounded before the hop sum here, fused there (hout, K > 1); an accumulating slot's old value follows the segment's last
+// pair here, agg_bwd_kernel's chunked loop adds it behind the hop's first PF pairs, where it arrives.
 //   forward : the KP-GIN+ training epilogue only (GELU, theta from alphas or given, dictionary P, code tables, S saved, per-hop
 //             slot inputs) - the configuration `FAST` of aggregate.hip;
 //   backward: the plain transposed gather gx = sum g[dst] into per-hop slot outputs (accumulate_mask honoured).
@@ -220,6 +222,7 @@ int agg_small_fwd(const kpgnn_agg_fwd_desc* d, hipStream_t s, bool* handled) {
     *handled = true;
     hipLaunchKernelGGL(agg_fwd_small_kernel, dim3((unsigned)d->N), dim3(kBlockS), 0, s, p);
     KPGNN_LAUNCH_CHECK("agg_fwd_small_kernel");
+    agg_route_bump(0, KPGNN_AGG_ROUTE_SMALL);
     return KPGNN_OK;
 }
 
@@ -243,6 +246,7 @@ int agg_small_bwd(const kpgnn_agg_bwd_desc* d, hipStream_t s, bool* handled) {
     *handled = true;
     hipLaunchKernelGGL(agg_bwd_small_kernel, dim3((unsigned)d->N), dim3(kBlockS), 0, s, p);
     KPGNN_LAUNCH_CHECK("agg_bwd_small_kernel");
+    agg_route_bump(1, KPGNN_AGG_ROUTE_SMALL);
     return KPGNN_OK;
 }
 

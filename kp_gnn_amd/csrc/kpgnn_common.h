@@ -170,6 +170,10 @@ int agg_narrow_bwd(const kpgnn_agg_bwd_desc* d, hipStream_t s, bool* handled);
 // A graph's hop slab staged in LDS, for dense K-hop neighbourhoods (aggregate_lds.hip; needs desc.graph_ptr): *handled as above.
 int agg_lds_fwd(const kpgnn_agg_fwd_desc* d, hipStream_t s, bool* handled);
 int64_t agg_lds_launch_count();     // launches done there since the library was loaded (host-side counter)
+// Host-side counters of which kernel served a kpgnn_aggregate_fwd (bwd = 0) / kpgnn_aggregate_bwd (bwd = 1) call, by
+// KPGNN_AGG_ROUTE_* (kpgnn_agg_launch_counts); bumped where the kernel is launched (aggregate_lds.hip holds them)
+void agg_route_bump(int bwd, int route);
+int64_t agg_route_count(int bwd, int route);
 // One block per node, one unit per hop, for small batches (aggregate_small.hip): *handled as above.
 int agg_small_fwd(const kpgnn_agg_fwd_desc* d, hipStream_t s, bool* handled);
 int agg_small_bwd(const kpgnn_agg_bwd_desc* d, hipStream_t s, bool* handled);

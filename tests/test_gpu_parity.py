@@ -197,7 +197,11 @@ def _random_khop(N, E, K, seed, n0=5, nk=12, density=0.3):
 @pytest.mark.parametrize("D", [1, 2, 3, 6, 13, 16, 20, 33, 40, 64, 104, 120, 256])
 @pytest.mark.parametrize("mode", ["gin", "ginplus", "gcn", "sum"])
 def test_aggregate_modes_and_widths_vs_oracle(D, mode):
-    """Every (VEC, sub-group) kernel shape and epilogue, fwd + bwd, against the materialised CPU sequence."""
+    """Every epilogue at thirteen row widths, fwd + bwd, against the materialised CPU sequence.  Which kernel a width reaches is
+    asserted from kpgnn_agg_launch_counts: D <= 32 outside GCN is served by agg_narrow_kernel in both directions (the table
+    gradients of those modes come from kpgnn_table_grad, so the gather is asked for none), every other (D, mode) by the
+    sub-group kernels agg_fwd_kernel / agg_bwd_kernel - for D = 1 .. 20 those run in GCN mode only here; all their row shapes and
+    epilogues are held to float64 on hard graphs by tests/test_gather_row_shapes.py."""
     from oracle import kp_layers_oracle as LO
     from kp_gnn_amd import _lib
     from kp_gnn_amd.khop_csr import KHopCSR
@@ -239,8 +243,13 @@ def test_aggregate_modes_and_widths_vs_oracle(D, mode):
     csr = KHopCSR.build(ei.to(dev), ea.to(dev), N)
     xd, t0d, tkd, Pd = (t.clone().to(dev).requires_grad_(True) for t in (x, t0, tk, P))
     m = {"gin": _lib.MODE_GIN, "ginplus": _lib.MODE_GINPLUS, "gcn": _lib.MODE_GCN, "sum": _lib.MODE_SUM}[mode]
+    before = _lib.agg_launch_counts()
     out = khop_aggregate(xd, csr, K, m, table0=t0d, tablek=tkd, periph=Pd, eps=eps.to(dev) if mode == "gin" else None)
     (out * w.to(dev)).sum().backward()
+    route = _lib.ROUTE_NARROW if D <= 32 and mode != "gcn" else _lib.ROUTE_SUBGROUP
+    after = _lib.agg_launch_counts()
+    for name, b, a in zip(("forward", "backward"), before, after):
+        assert [y - x for x, y in zip(b, a)] == [int(r == route) for r in range(4)], (name, "route counters", b, a)
     T = TOL["aggregate"]
     _close(out, ref, "out", **T["out"])
     _close(xd.grad, xo.grad, "grad_x", **T["grad_x"])
