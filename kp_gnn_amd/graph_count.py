@@ -11,11 +11,9 @@ keep the reference's answer.  The reading of the .mat file, the index vectors an
 import numpy as np
 import torch
 
+from .raw_graphs import RawGraphs
+
 COUNT_LABELS = ("tri", "tailed", "star", "cyc4", "cus")
-
-
-def _i64(a):
-    return np.ascontiguousarray(np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.int64)).reshape(-1)
 
 
 def check_graph(g, n, ei):
@@ -43,16 +41,8 @@ def labels_one(n, ei):
 
 
 def _split(node_ptr, edge_ptr, edge_index):
-    node_ptr, edge_ptr = _i64(node_ptr), _i64(edge_ptr)
-    G = node_ptr.shape[0] - 1
-    if G < 0 or edge_ptr.shape[0] != G + 1:
-        raise ValueError("node_ptr and edge_ptr must both have G + 1 entries")
-    if node_ptr[0] != 0 or edge_ptr[0] != 0 or bool((np.diff(node_ptr) < 0).any()) or bool((np.diff(edge_ptr) < 0).any()):
-        raise ValueError("node_ptr / edge_ptr must start at 0 and not decrease")
-    ei = np.asarray(edge_index.cpu() if torch.is_tensor(edge_index) else edge_index, dtype=np.int64).reshape(2, -1)
-    if ei.shape[1] != int(edge_ptr[-1]):
-        raise ValueError("edge_index does not match edge_ptr")
-    return node_ptr, edge_ptr, ei
+    g = RawGraphs(node_ptr, edge_ptr, edge_index)
+    return g.node_ptr, g.edge_ptr, g.edge_index_host()
 
 
 def count_labels_host_f64(node_ptr, edge_ptr, edge_index, graphs=None):

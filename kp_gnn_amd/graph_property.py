@@ -17,12 +17,10 @@ import math
 import numpy as np
 import torch
 
+from .raw_graphs import RawGraphs, i64
+
 NODE_LABELS = ("sssp", "eccentricity", "graph_laplacian_features")
 GRAPH_LABELS = ("is_connected", "diameter", "spectral_radius")
-
-
-def _i64(a):
-    return np.ascontiguousarray(np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.int64)).reshape(-1)
 
 
 def check_graph(g, n, ei, s):
@@ -82,22 +80,14 @@ def labels_one(n, ei, F, s):
 
 
 def _split(node_ptr, edge_ptr, edge_index, features, source):
-    node_ptr, edge_ptr, source = _i64(node_ptr), _i64(edge_ptr), _i64(source)
-    G = node_ptr.shape[0] - 1
-    if G < 0 or edge_ptr.shape[0] != G + 1 or source.shape[0] != G:
-        raise ValueError("node_ptr and edge_ptr must have G + 1 entries and source G")
-    if node_ptr[0] != 0 or edge_ptr[0] != 0 or bool((np.diff(node_ptr) < 0).any()) or bool((np.diff(edge_ptr) < 0).any()):
-        raise ValueError("node_ptr / edge_ptr must start at 0 and not decrease")
-    ei = np.asarray(edge_index.cpu() if torch.is_tensor(edge_index) else edge_index, dtype=np.int64).reshape(2, -1)
-    if ei.shape[1] != int(edge_ptr[-1]):
-        raise ValueError("edge_index does not match edge_ptr")
+    g = RawGraphs(node_ptr, edge_ptr, edge_index, source=source)
     F = np.asarray(features.cpu() if torch.is_tensor(features) else features)
     if F.dtype not in (np.float32, np.float64):
         raise ValueError("features must be float32 or float64")
     F = F.astype(np.float64).reshape(-1)
-    if F.shape[0] != int(node_ptr[-1]):
+    if F.shape[0] != g.N:
         raise ValueError("features does not match node_ptr")
-    return node_ptr, edge_ptr, ei, F, source
+    return g.node_ptr, g.edge_ptr, g.edge_index_host(), F, g.source
 
 
 def labels_host_f64(node_ptr, edge_ptr, edge_index, features, source, graphs=None):
@@ -128,8 +118,8 @@ def graph_property_labels_host(node_ptr, edge_ptr, edge_index, features, source,
 def normalize_labels(node_labels, graph_labels, node_ptr, train_ids):
     """GraphPropertyDataset.process: every label column divided by its maximum over the TRAINING graphs `train_ids` (node
     columns: over their nodes).  Plain torch division, so a column whose training maximum is 0 gives 0 / 0 = nan as there."""
-    ptr = torch.as_tensor(_i64(node_ptr))
-    ids = torch.as_tensor(_i64(train_ids))
+    ptr = torch.as_tensor(i64(node_ptr))
+    ids = torch.as_tensor(i64(train_ids))
     rows = torch.cat([torch.arange(int(ptr[g]), int(ptr[g + 1])) for g in ids.tolist()]) if ids.numel() else ids
     max_node = node_labels[rows.to(node_labels.device)].max(0)[0]
     max_graph = graph_labels[ids.to(graph_labels.device)].max(0)[0]
@@ -139,7 +129,7 @@ def normalize_labels(node_labels, graph_labels, node_ptr, train_ids):
 def source_features(x_feature, source, node_ptr):
     """The reference's node input [one-hot(source), feature] as float32 [N,2] (GenerateGraphPropertyDataset: to_categorical of
     the source node stacked with the random feature), on x_feature's device."""
-    ptr, source = _i64(node_ptr), _i64(source)
+    ptr, source = i64(node_ptr), i64(source)
     x_feature = torch.as_tensor(x_feature)
     out = torch.zeros((int(ptr[-1]), 2), dtype=torch.float32, device=x_feature.device)
     if bool(((source < 0) | (source >= np.diff(ptr))).any()):

@@ -8,6 +8,8 @@ import torch
 
 from . import _lib
 from ._lib import MODE_GCN, MODE_GIN, MODE_GINPLUS, MODE_SUM, LaunchTimer, set_launch_timer  # noqa: F401
+from .ops_dataset import (COUNT_LABELS_AUTO, GRAPH_LABELS_AUTO, count_labels, count_labels_launch, graph_labels_launch,  # noqa: F401
+                          graph_property_labels, khop_transform, resistance_distance)
 
 _SQRT1_2 = 0.7071067811865476
 _INV_SQRT_2PI = 0.3989422804014327
@@ -2139,430 +2141,6 @@ def body_norm(x, kind, weight=None, bias=None, residual=None, eps=1e-5):
     if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (x, weight, bias, residual)):
         return _norm_fwd_launch(x.detach(), kind, weight, bias, residual, eps)[0]      # no autograd node, nothing saved
     return BodyNorm.apply(x, weight, bias, residual, kind, eps)
-
-
-# ------------------------------------------------------------------------------------------------ resistance distance
-def _host_i64(a):
-    return np.ascontiguousarray(np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.int64)).reshape(-1)
-
-
-def _rd_large_chunks(ids, nodes, slab_bytes, workspace_bytes):
-    """`ids` (graphs of 129 .. RD_LARGE_MAX_NODES nodes, in call order) cut into runs whose slabs - each sized for the run's
-    largest graph - fit `workspace_bytes`; a graph that does not fit alone is a run of its own.  [(ids, max_nodes, bytes)]."""
-    out, i = [], 0
-    while i < ids.size:
-        j, cap = i + 1, int(nodes[ids[i]])
-        while j < ids.size:
-            c = max(cap, int(nodes[ids[j]]))
-            if (j + 1 - i) * slab_bytes(c) > workspace_bytes:
-                break
-            j, cap = j + 1, c
-        out.append((ids[i:j], cap, (j - i) * slab_bytes(cap)))
-        i = j
-    return out
-
-
-def resistance_distance(node_ptr, edge_ptr, edge_index, device, large="host", workspace_bytes=1 << 30):
-    """The reference's `rd` node feature (data_utils.py:280-303) of G graphs at once: (rd [N,1] float32 on `device`, status
-    [G] int32 on the host).  node_ptr / edge_ptr [G+1]: host offsets of each graph's nodes and edges; edge_index [2,E] int64
-    (host or device): ids global within the call, edges grouped by graph.  The graphs are bucketed by size on the host, one
-    kpgnn_resistance_distance launch per class (n <= 32: a wavefront per graph; n <= 128: a block per graph), and `status` is
-    read back once.  It tells which graphs the kernel served (0); those it did not - a directed list (1), more nodes than the
-    kernels serve (2), a failed pivot (3) - are filled from khop_transform.resistance_distance_host, and an edge endpoint
-    outside its graph (4) raises IndexError before anything else is launched or filled.
-    large: who serves a graph of more than 128 nodes.  "host": nobody on the device - it gets status 2 from the block-class
-    launch and the float64 host route fills it.  "device": a third class, 128 < n <= 2048, goes to
-    kpgnn_resistance_distance_large (csrc/resistance_large.hip: the matrix in a device workspace, blocked Gauss-Jordan), in
-    runs of graphs whose slabs fit `workspace_bytes` (one graph always runs, whatever it needs), one launch per run on one
-    workspace allocated once per call; status 2 is then n > 2048.  The two are different float64 computations: their float32
-    roundings may differ in the last bit."""
-    if large not in ("host", "device"):
-        raise ValueError(f"unknown large {large!r}")
-    node_ptr, edge_ptr = _host_i64(node_ptr), _host_i64(edge_ptr)
-    G = node_ptr.shape[0] - 1
-    if G < 0 or edge_ptr.shape[0] != G + 1:
-        raise ValueError("node_ptr and edge_ptr must both have G + 1 entries")
-    if node_ptr[0] != 0 or edge_ptr[0] != 0 or bool((np.diff(node_ptr) < 0).any()) or bool((np.diff(edge_ptr) < 0).any()):
-        raise ValueError("node_ptr / edge_ptr must start at 0 and not decrease")
-    N, E = int(node_ptr[-1]), int(edge_ptr[-1])
-    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.shape[1] != E:
-        raise ValueError("edge_index does not match edge_ptr")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise _lib.KpgnnError("ops.resistance_distance is the device route: khop_transform.resistance_distance_host is the host one")
-    out = torch.zeros((N, 1), dtype=torch.float32, device=dev)
-    status = np.zeros(G, dtype=np.int32)
-    if G == 0:
-        return out, torch.from_numpy(status)
-    ei = edge_index.to(device=dev, dtype=torch.int64).contiguous()
-    nptr, eptr = torch.from_numpy(node_ptr).to(dev), torch.from_numpy(edge_ptr).to(dev)
-    st = torch.empty(G, dtype=torch.int32, device=dev)
-    nodes = np.diff(node_ptr)
-    keep = []
-    block_class = nodes > _lib.RD_WAVE_NODES
-    if large == "device":
-        big = np.flatnonzero((nodes > _lib.RD_MAX_NODES) & (nodes <= _lib.RD_LARGE_MAX_NODES))
-        block_class = block_class & ((nodes <= _lib.RD_MAX_NODES) | (nodes > _lib.RD_LARGE_MAX_NODES))
-    for ids in (np.flatnonzero(nodes <= _lib.RD_WAVE_NODES), np.flatnonzero(block_class)):
-        if ids.size == 0:
-            continue
-        ids_d = torch.from_numpy(ids.astype(np.int32)).to(dev)
-        keep.append(ids_d)
-        d = _lib.RdDesc()
-        d.G, d.n_ids, d.E = G, ids.size, E
-        d.node_ptr, d.edge_ptr, d.edge_index, d.graph_ids = nptr.data_ptr(), eptr.data_ptr(), ei.data_ptr(), ids_d.data_ptr()
-        d.max_nodes = max(1, min(_lib.RD_MAX_NODES, int(nodes[ids].max())))     # (larger graphs get status 2 from the kernel)
-        d.out, d.status = out.data_ptr(), st.data_ptr()
-        _lib.launch("kpgnn_resistance_distance", dev, ctypes.byref(d))
-    if large == "device" and big.size:
-        slab = lambda cap: int(_lib.load().kpgnn_rd_large_workspace_bytes(cap, 1))  # noqa: E731
-        runs = _rd_large_chunks(big, nodes, slab, int(workspace_bytes))
-        ws = torch.empty(max(r[2] for r in runs), dtype=torch.uint8, device=dev)
-        keep.append(ws)
-        for ids, cap, nbytes in runs:
-            ids_d = torch.from_numpy(ids.astype(np.int32)).to(dev)
-            keep.append(ids_d)
-            d = _lib.RdLargeDesc()
-            d.G, d.n_ids, d.E, d.max_nodes = G, ids.size, E, cap
-            d.node_ptr, d.edge_ptr, d.edge_index, d.graph_ids = nptr.data_ptr(), eptr.data_ptr(), ei.data_ptr(), ids_d.data_ptr()
-            d.out, d.status = out.data_ptr(), st.data_ptr()
-            d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
-            _lib.launch("kpgnn_resistance_distance_large", dev, ctypes.byref(d))
-    status = st.cpu()
-    del keep
-    bad = status.numpy()
-    if bool((bad == _lib.RD_RANGE).any()):
-        g = int(np.flatnonzero(bad == _lib.RD_RANGE)[0])
-        raise IndexError(f"graph {g}: an edge endpoint lies outside its nodes [{node_ptr[g]}, {node_ptr[g + 1]})")
-    todo = np.flatnonzero(bad != 0)
-    if todo.size:
-        from .khop_transform import resistance_distance_host
-        ei_h = edge_index.cpu() if edge_index.is_cuda else edge_index
-        ei_h = ei_h.numpy()
-        rows, vals = [], []
-        for g in todo:
-            n0, n1, e0, e1 = node_ptr[g], node_ptr[g + 1], edge_ptr[g], edge_ptr[g + 1]
-            rows.append(np.arange(n0, n1))
-            vals.append(resistance_distance_host(n1 - n0, ei_h[:, e0:e1] - n0).astype(np.float32))
-        out[torch.from_numpy(np.concatenate(rows)).to(dev), 0] = torch.from_numpy(np.concatenate(vals)).to(dev)
-    return out, status
-
-
-# ------------------------------------------------------------------------------------------------ graph-property labels
-GRAPH_LABELS_AUTO = "device"     # graph_property_labels(route="auto"): DESIGN.md 5.24 has the measurement behind it
-
-
-def graph_labels_launch(G, nptr, eptr, ei, E, feat, src, ids, max_nodes, node_out, graph_out, status):
-    """One kpgnn_graph_labels launch over device tensors: the graphs `ids` (int32) of a call of G graphs, sized for max_nodes."""
-    d = _lib.GraphLabelsDesc()
-    d.G, d.n_ids, d.E, d.max_nodes = G, ids.numel(), E, max_nodes
-    d.node_ptr, d.edge_ptr, d.edge_index, d.graph_ids = nptr.data_ptr(), eptr.data_ptr(), ei.data_ptr(), ids.data_ptr()
-    d.features, d.source = feat.data_ptr(), src.data_ptr()
-    d.node_out, d.graph_out, d.status = node_out.data_ptr(), graph_out.data_ptr(), status.data_ptr()
-    _lib.launch("kpgnn_graph_labels", node_out.device, ctypes.byref(d))
-
-
-def graph_property_labels(node_ptr, edge_ptr, edge_index, features, source, device, route="auto"):
-    """The labels of the reference's graph- and node-property dataset (datasets/GraphPropertyDataset.py genereate_dataset) of G
-    raw graphs at once: (node_labels [N,3] float32: sssp | eccentricity | laplacian features, graph_labels [G,3] float32:
-    is_connected | diameter | spectral_radius), both on `device`.  node_ptr / edge_ptr [G+1]: host offsets; edge_index [2,E]
-    int64 LOCAL ids, edges grouped by graph (host or device); features [N] float32 or float64 (widened to double, which is
-    exact); source [G] the local id of each graph's source node.
-    route "device": the graphs are bucketed by size on the host, one kpgnn_graph_labels launch per class (n <= 32: a
-    wavefront per graph; n <= 64: a block per graph), and `status` is read back once.  Graphs the kernel did not serve - a
-    directed list (1), more than 64 nodes (2) - are filled from graph_property.labels_host_f64 inside the same call; an edge
-    endpoint outside its graph (3), a self loop (4) and a source outside its graph (5) raise ValueError naming the first such
-    graph.  route "host": graph_property.graph_property_labels_host, moved to the device.  "auto" is GRAPH_LABELS_AUTO.  The
-    integer labels are the same whichever route served a graph; the two float64 computations of the spectral radius and of
-    the laplacian column may differ in the last float32 bit."""
-    if route not in ("auto", "device", "host"):
-        raise ValueError(f"unknown route {route!r}")
-    from . import graph_property as GP
-    route = GRAPH_LABELS_AUTO if route == "auto" else route
-    dev = torch.device(device)
-    if route == "host":
-        return GP.graph_property_labels_host(node_ptr, edge_ptr, edge_index, features, source, dev)
-    if dev.type != "cuda":
-        raise _lib.KpgnnError("ops.graph_property_labels(route='device') needs a GPU device: graph_property_labels_host is the host route")
-    node_ptr, edge_ptr, src_h = _host_i64(node_ptr), _host_i64(edge_ptr), _host_i64(source)
-    G = node_ptr.shape[0] - 1
-    if G < 0 or edge_ptr.shape[0] != G + 1 or src_h.shape[0] != G:
-        raise ValueError("node_ptr and edge_ptr must have G + 1 entries and source G")
-    if node_ptr[0] != 0 or edge_ptr[0] != 0 or bool((np.diff(node_ptr) < 0).any()) or bool((np.diff(edge_ptr) < 0).any()):
-        raise ValueError("node_ptr / edge_ptr must start at 0 and not decrease")
-    N, E = int(node_ptr[-1]), int(edge_ptr[-1])
-    if not torch.is_tensor(edge_index):
-        edge_index = torch.from_numpy(np.ascontiguousarray(np.asarray(edge_index, dtype=np.int64)))
-    edge_index = edge_index.reshape(2, -1)
-    if edge_index.shape[1] != E:
-        raise ValueError("edge_index does not match edge_ptr")
-    if not torch.is_tensor(features):
-        features = torch.from_numpy(np.ascontiguousarray(features))
-    if features.dtype not in (torch.float32, torch.float64) or features.numel() != N:
-        raise ValueError("features must be [N] float32 or float64")
-    node_out = torch.zeros((N, 3), dtype=torch.float32, device=dev)
-    graph_out = torch.zeros((G, 3), dtype=torch.float32, device=dev)
-    if G == 0:
-        return node_out, graph_out
-    ei = edge_index.to(device=dev, dtype=torch.int64).contiguous()
-    feat = features.reshape(-1).to(device=dev, dtype=torch.float64).contiguous()
-    src = torch.from_numpy(np.clip(src_h, -1, 1 << 30).astype(np.int32)).to(dev)      # (any value outside [0, n) is status 5)
-    nptr, eptr = torch.from_numpy(node_ptr).to(dev), torch.from_numpy(edge_ptr).to(dev)
-    st = torch.empty(G, dtype=torch.int32, device=dev)
-    nodes = np.diff(node_ptr)
-    keep = []
-    for ids in (np.flatnonzero(nodes <= _lib.GL_WAVE_NODES), np.flatnonzero(nodes > _lib.GL_WAVE_NODES)):
-        if ids.size == 0:
-            continue
-        ids_d = torch.from_numpy(ids.astype(np.int32)).to(dev)
-        keep.append(ids_d)
-        cap = max(1, min(_lib.GL_MAX_NODES, int(nodes[ids].max())))         # (larger graphs get status 2 from the kernel)
-        graph_labels_launch(G, nptr, eptr, ei, E, feat, src, ids_d, cap, node_out, graph_out, st)
-    bad = st.cpu().numpy()
-    del keep
-    refused = np.flatnonzero(bad >= _lib.GL_ENDPOINT)
-    if refused.size:
-        g = int(refused[0])
-        what = {_lib.GL_ENDPOINT: f"an edge endpoint lies outside its nodes [0, {int(nodes[g])})",
-                _lib.GL_SELF_LOOP: "a self loop (the labels are defined for graphs without one)",
-                _lib.GL_SOURCE: f"source {int(src_h[g])} lies outside its nodes [0, {int(nodes[g])})"}[int(bad[g])]
-        raise ValueError(f"graph {g}: {what}")
-    todo = np.flatnonzero(bad != 0)
-    if todo.size:
-        node_h, graph_h = GP.labels_host_f64(node_ptr, edge_ptr, edge_index, features, src_h, graphs=todo)
-        rows = torch.from_numpy(np.concatenate([np.arange(node_ptr[g], node_ptr[g + 1]) for g in todo])).to(dev)
-        node_out[rows] = torch.from_numpy(node_h[rows.cpu().numpy()].astype(np.float32)).to(dev)
-        gi = torch.from_numpy(todo).to(dev)
-        graph_out[gi] = torch.from_numpy(graph_h[todo].astype(np.float32)).to(dev)
-    return node_out, graph_out
-
-
-# ------------------------------------------------------------------------------------------------ substructure-count labels
-COUNT_LABELS_AUTO = "device"      # count_labels(route="auto"): DESIGN.md 5.25 has the measurement behind it
-
-
-def count_labels_launch(G, nptr, eptr, ei, E, ids, max_nodes, out, status, workspace=None, workspace_bytes=0):
-    """One kpgnn_count_labels launch over device tensors: the graphs `ids` (int32) of a call of G graphs, sized for max_nodes
-    (which picks the size class); `workspace` (uint8) holds a slab per id when max_nodes > CL_WORD_NODES."""
-    d = _lib.CountLabelsDesc()
-    d.G, d.n_ids, d.E, d.max_nodes = G, ids.numel(), E, max_nodes
-    d.node_ptr, d.edge_ptr, d.edge_index, d.graph_ids = nptr.data_ptr(), eptr.data_ptr(), ei.data_ptr(), ids.data_ptr()
-    d.out, d.status = out.data_ptr(), status.data_ptr()
-    d.workspace, d.workspace_bytes = (workspace.data_ptr() if workspace is not None else None), int(workspace_bytes)
-    _lib.launch("kpgnn_count_labels", out.device, ctypes.byref(d))
-
-
-def count_labels(node_ptr, edge_ptr, edge_index, device, route="auto", workspace_bytes=1 << 28):
-    """The labels of the reference's substructure-counting dataset (datasets/GraphCountDataset.py process) of G raw graphs at
-    once: y [G,5] float64 on `device`, tri | tailed | star | cyc4 | cus.  node_ptr / edge_ptr [G+1]: host offsets; edge_index
-    [2,E] int64 LOCAL ids, edges grouped by graph (host or device).
-    route "device": the graphs are bucketed by size on the host, one kpgnn_count_labels launch per class (n <= 32: a wavefront
-    per graph; n <= 64: a block per graph; n <= 2048: a block per graph on a slab of a device workspace, in runs of graphs
-    whose slabs fit `workspace_bytes` - one graph always runs - on one workspace allocated once per call), and `status` is
-    read back once.  Graphs the kernel did not serve - a directed list (1), a self loop (2), more than 2048 nodes (3) - are
-    filled from graph_count.count_labels_host_f64 inside the same call; an edge endpoint outside its graph (4) raises
-    ValueError naming the first such graph.  route "host": graph_count.count_labels_host, moved to the device.  "auto" is
-    COUNT_LABELS_AUTO.  The four integer labels are the same whichever route served a graph; the two float64 sums of cus may
-    differ in their last bits."""
-    if route not in ("auto", "device", "host"):
-        raise ValueError(f"unknown route {route!r}")
-    from . import graph_count as GCN
-    route = COUNT_LABELS_AUTO if route == "auto" else route
-    dev = torch.device(device)
-    if route == "host":
-        return GCN.count_labels_host(node_ptr, edge_ptr, edge_index, dev)
-    if dev.type != "cuda":
-        raise _lib.KpgnnError("ops.count_labels(route='device') needs a GPU device: graph_count.count_labels_host is the host route")
-    node_ptr, edge_ptr = _host_i64(node_ptr), _host_i64(edge_ptr)
-    G = node_ptr.shape[0] - 1
-    if G < 0 or edge_ptr.shape[0] != G + 1:
-        raise ValueError("node_ptr and edge_ptr must both have G + 1 entries")
-    if node_ptr[0] != 0 or edge_ptr[0] != 0 or bool((np.diff(node_ptr) < 0).any()) or bool((np.diff(edge_ptr) < 0).any()):
-        raise ValueError("node_ptr / edge_ptr must start at 0 and not decrease")
-    E = int(edge_ptr[-1])
-    if not torch.is_tensor(edge_index):
-        edge_index = torch.from_numpy(np.ascontiguousarray(np.asarray(edge_index, dtype=np.int64)))
-    edge_index = edge_index.reshape(2, -1)
-    if edge_index.shape[1] != E:
-        raise ValueError("edge_index does not match edge_ptr")
-    out = torch.zeros((G, 5), dtype=torch.float64, device=dev)
-    if G == 0:
-        return out
-    ei = edge_index.to(device=dev, dtype=torch.int64).contiguous()
-    nptr, eptr = torch.from_numpy(node_ptr).to(dev), torch.from_numpy(edge_ptr).to(dev)
-    nodes = np.diff(node_ptr)
-    # (no launch for a graph above the cap: its status is set here; -1 marks a graph no launch wrote, which is an error below)
-    st = torch.from_numpy(np.where(nodes > _lib.CL_MAX_NODES, _lib.CL_TOO_LARGE, -1).astype(np.int32)).to(dev)
-    keep = []
-    word = nodes <= _lib.CL_WORD_NODES
-    for ids, cap in ((np.flatnonzero(nodes <= _lib.CL_WAVE_NODES), _lib.CL_WAVE_NODES),
-                     (np.flatnonzero(word & (nodes > _lib.CL_WAVE_NODES)), _lib.CL_WORD_NODES)):
-        if ids.size == 0:
-            continue
-        ids_d = torch.from_numpy(ids.astype(np.int32)).to(dev)
-        keep.append(ids_d)
-        count_labels_launch(G, nptr, eptr, ei, E, ids_d, cap, out, st)
-    big = np.flatnonzero(~word & (nodes <= _lib.CL_MAX_NODES))
-    if big.size:
-        slab = lambda cap: int(_lib.load().kpgnn_count_labels_workspace_bytes(cap))  # noqa: E731
-        runs = _rd_large_chunks(big, nodes, slab, int(workspace_bytes))
-        ws = torch.empty(max(r[2] for r in runs), dtype=torch.uint8, device=dev)
-        keep.append(ws)
-        for ids, cap, nbytes in runs:
-            ids_d = torch.from_numpy(ids.astype(np.int32)).to(dev)
-            keep.append(ids_d)
-            count_labels_launch(G, nptr, eptr, ei, E, ids_d, cap, out, st, ws, nbytes)
-    bad = st.cpu().numpy()
-    del keep
-    refused = np.flatnonzero(bad == _lib.CL_ENDPOINT)
-    if refused.size:
-        g = int(refused[0])
-        raise ValueError(f"graph {g}: an edge endpoint lies outside its nodes [0, {int(nodes[g])})")
-    if bool((bad < 0).any()):
-        raise _lib.KpgnnError(f"kpgnn_count_labels left graph {int(np.flatnonzero(bad < 0)[0])} without a status")
-    todo = np.flatnonzero(bad != _lib.CL_OK)
-    if todo.size:
-        y = GCN.count_labels_host_f64(node_ptr, edge_ptr, edge_index, graphs=todo)
-        out[torch.from_numpy(todo).to(dev)] = torch.from_numpy(y[todo]).to(dev)
-    return out
-
-
-# ------------------------------------------------------------------------------------------------ the K-hop pre-transform
-def khop_transform(node_ptr, edge_ptr, edge_index, edge_attr, K, max_edge_attr_num, max_hop_num, max_edge_type,
-                   max_edge_count, max_distance_count, kernel, device, large="host"):
-    """khop_transform.khop_batch on the device: (the same dict of collated int64 tensors, on `device`; status [G] int32 on the
-    host).  node_ptr / edge_ptr [G+1]: host offsets; edge_index [2,E] LOCAL ids and edge_attr [E] or None, host or device.
-    The graphs are bucketed by size (n <= 32: a wavefront per graph; n <= 64: a block per graph), kpgnn_khop_dev_count runs per
-    class, the per-graph edge counts and `status` come back in ONE read, the degrees are scanned with cumsum, and
-    kpgnn_khop_dev_fill writes the tensors.  Graphs the kernel did not serve - more than 64 nodes (1), a summed edge type above
-    63 (4), K / max_edge_type / max_hop_num beyond 16 / 8 / 8 (5) - go through khop_batch on the host: their edge counts join
-    the scan and their slices are copied in, so the result is the same whichever route served a graph.  A walk count >= 2^31
-    (2) raises what khop_batch raises for that graph (KpgnnError), an edge endpoint outside its graph (3) ValueError.
-    large="device": the graphs of more than 64 and at most KHOP_LARGE_MAX_NODES nodes are a third class, served inside the same
-    call by kpgnn_khop_large_count / _fill (a wavefront per source row, csrc/khop_large.hip): their degrees join the same scan
-    and the same read, their status is 0, and only graphs above that cap, 4 and 5 go to the host.  "host", the default, leaves
-    every graph above 64 nodes to khop_batch.  The tensors are the same bits either way."""
-    if large not in ("host", "device"):
-        raise ValueError(f"unknown large {large!r}: 'host' or 'device'")
-    from . import khop_transform as KT
-    node_ptr, edge_ptr = _host_i64(node_ptr), _host_i64(edge_ptr)
-    G = node_ptr.shape[0] - 1
-    if G < 0 or edge_ptr.shape[0] != G + 1:
-        raise ValueError("node_ptr and edge_ptr must both have G + 1 entries")
-    if node_ptr[0] != 0 or edge_ptr[0] != 0 or bool((np.diff(node_ptr) < 0).any()) or bool((np.diff(edge_ptr) < 0).any()):
-        raise ValueError("node_ptr / edge_ptr must start at 0 and not decrease")
-    N, E = int(node_ptr[-1]), int(edge_ptr[-1])
-    if not torch.is_tensor(edge_index):
-        edge_index = torch.from_numpy(np.ascontiguousarray(np.asarray(edge_index, dtype=np.int64)))
-    edge_index = edge_index.reshape(2, -1)
-    if edge_index.shape[1] != E:
-        raise ValueError("edge_index does not match edge_ptr")
-    if edge_attr is not None:
-        if not torch.is_tensor(edge_attr):
-            edge_attr = torch.from_numpy(np.ascontiguousarray(np.asarray(edge_attr, dtype=np.int64)))
-        edge_attr = edge_attr.reshape(-1)
-        if edge_attr.shape[0] != E:
-            raise ValueError("edge_attr does not match edge_ptr")
-    if kernel not in ("spd", "gd"):
-        raise ValueError(f"unknown kernel {kernel!r}")
-    if K < 1 or min(max_edge_attr_num, max_hop_num, max_edge_type, max_edge_count, max_distance_count) < 0:
-        raise ValueError("bad K-hop arguments")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise _lib.KpgnnError("ops.khop_transform is the device route: khop_transform.khop_batch is the host one")
-    args = (K, max_edge_attr_num, max_hop_num, max_edge_type, max_edge_count, max_distance_count, kernel)
-    want_p = max_hop_num > 0 and max_edge_type > 0
-    i64 = dict(dtype=torch.int64, device=dev)
-    ei = edge_index.to(**i64).contiguous()
-    ea = None if edge_attr is None else edge_attr.to(**i64).contiguous()
-    nptr, eptr = torch.from_numpy(node_ptr).to(dev), torch.from_numpy(edge_ptr).to(dev)
-    st = torch.zeros(G, dtype=torch.int32, device=dev)
-    ws = torch.zeros(max(2 * N, 1), **i64)                  # [0, N) any-hop masks, [N, 2N) K-hop out-degrees
-    nodes = np.diff(node_ptr)
-    d = _lib.KhopDevDesc()
-    d.G, d.N, d.E_in = G, N, E
-    d.node_ptr, d.edge_ptr, d.edge_index = nptr.data_ptr(), eptr.data_ptr(), ei.data_ptr()
-    d.edge_attr = None if ea is None else ea.data_ptr()
-    d.K, d.max_edge_attr_num, d.max_hop_num, d.max_edge_type, d.max_edge_count, d.max_distance_count = args[:6]
-    d.kernel = 0 if kernel == "spd" else 1
-    d.workspace, d.workspace_bytes, d.status = ws.data_ptr(), ws.numel() * 8, st.data_ptr()
-    classes = []
-    block = nodes > _lib.KHOP_WAVE_NODES
-    if large == "device":
-        block &= nodes <= _lib.KHOP_MAX_NODES
-    for ids in (np.flatnonzero(nodes <= _lib.KHOP_WAVE_NODES), np.flatnonzero(block)):
-        if ids.size:
-            classes.append(("kpgnn_khop_dev", torch.from_numpy(ids.astype(np.int32)).to(dev), ids.size,
-                            max(1, min(_lib.KHOP_MAX_NODES, int(nodes[ids].max()))), ws))  # (larger graphs get status 1)
-    ws_l = None
-    ids = np.flatnonzero(nodes > _lib.KHOP_MAX_NODES) if large == "device" else np.zeros(0, np.int64)
-    if ids.size:                                            # the third class: its own pair, its own workspace, degrees in front
-        cap = int(nodes[ids][nodes[ids] <= _lib.KHOP_LARGE_MAX_NODES].max(initial=_lib.KHOP_MAX_NODES + 1))
-        ws_l = torch.zeros(_lib.load().kpgnn_khop_large_workspace_bytes(N, E, cap) // 8, **i64)
-        classes.append(("kpgnn_khop_large", torch.from_numpy(ids.astype(np.int32)).to(dev), ids.size, cap, ws_l))
-
-    def run(pass_):
-        for pair, ids_d, n_ids, cap, w in classes:
-            d.graph_ids, d.n_ids, d.max_nodes = ids_d.data_ptr(), n_ids, cap
-            d.workspace, d.workspace_bytes = w.data_ptr(), w.numel() * 8
-            _lib.launch(pair + pass_, dev, ctypes.byref(d), timed=("khop_dev", lambda: 0))
-
-    run("_count")
-    deg = ws[N:2 * N]
-    if ws_l is not None:
-        deg += ws_l[:N]                                     # (0 wherever the large pair did not serve)
-    run_sum = torch.cat([deg.new_zeros(1), deg.cumsum(0)])
-    back = torch.cat([st.long(), run_sum[nptr[1:]] - run_sum[nptr[:-1]]]).cpu().numpy()         # the one read
-    status, g_edges = back[:G].astype(np.int32), back[G:].copy()
-    for code in (_lib.KHOP_ENDPOINT, _lib.KHOP_RANGE):
-        hit = np.flatnonzero(status == code)
-        if hit.size:
-            g = int(hit[0])
-            if code == _lib.KHOP_ENDPOINT:
-                raise ValueError(f"graph {g}: an edge endpoint lies outside its {int(nodes[g])} nodes")
-            sl = slice(int(edge_ptr[g]), int(edge_ptr[g + 1]))
-            KT.khop_batch([0, int(nodes[g])], [0, sl.stop - sl.start], edge_index[:, sl].cpu().numpy(),
-                          None if edge_attr is None else edge_attr[sl].cpu().numpy(), *args, num_threads=1)     # raises
-            raise _lib.KpgnnError(f"graph {g}: a walk count >= 2^31 within {K} hops")
-    todo = np.flatnonzero(status != 0)
-    host = None
-    if todo.size:                                           # the host route for what the kernel did not serve
-        ei_h = edge_index.cpu().numpy()
-        ea_h = None if edge_attr is None else edge_attr.cpu().numpy()
-        esl = [np.arange(edge_ptr[g], edge_ptr[g + 1]) for g in todo]
-        ecat = np.concatenate(esl)
-        h_nptr = np.concatenate([[0], np.cumsum(nodes[todo])])
-        h_eptr = np.concatenate([[0], np.cumsum([a.size for a in esl])])
-        host = KT.khop_batch(h_nptr, h_eptr, ei_h[:, ecat], None if ea_h is None else ea_h[ecat], *args)
-        g_edges[todo] = np.diff(host["edge_ptr"].numpy())
-        deg[torch.from_numpy(node_ptr[todo]).to(dev)] = torch.from_numpy(g_edges[todo]).to(dev)   # on the graph's first node
-    out_eptr = np.concatenate([[0], np.cumsum(g_edges)]).astype(np.int64)
-    E_out = int(out_eptr[-1])
-    node_off = deg.cumsum(0) - deg
-    out = {"edge_index": torch.empty((2, E_out), **i64), "edge_attr": torch.empty((E_out, K), **i64),
-           "pe_attr": torch.zeros((N, K - 1), **i64) if K > 1 else None,
-           "peripheral_edge_attr": torch.zeros((N, K, max_edge_type, 2), **i64) if want_p else None,
-           "peripheral_configuration_attr": torch.zeros((N, K, max_hop_num + 1), **i64) if want_p else None,
-           "batch": torch.empty(N, **i64), "edge_ptr": torch.from_numpy(out_eptr).to(dev), "node_ptr": nptr}
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
-    d.node_off, d.E_out = ptr(node_off), E_out
-    d.out_edge_index, d.out_edge_attr, d.out_pe_attr = ptr(out["edge_index"]), ptr(out["edge_attr"]), ptr(out["pe_attr"])
-    d.out_pea, d.out_pca = ptr(out["peripheral_edge_attr"]), ptr(out["peripheral_configuration_attr"])
-    d.out_batch = ptr(out["batch"])
-    run("_fill")
-    if host is not None:
-        h_off = host["edge_ptr"].numpy()
-        e_dst = np.concatenate([np.arange(out_eptr[g], out_eptr[g + 1]) for g in todo])
-        n_dst = np.concatenate([np.arange(node_ptr[g], node_ptr[g + 1]) for g in todo])
-        shift = np.repeat(node_ptr[todo] - h_nptr[:-1], np.diff(h_off))            # host ids -> ids of this call
-        e_dst, n_dst = torch.from_numpy(e_dst).to(dev), torch.from_numpy(n_dst).to(dev)
-        out["edge_index"][:, e_dst] = (host["edge_index"] + torch.from_numpy(shift)).to(dev)
-        out["edge_attr"][e_dst] = host["edge_attr"].to(dev)
-        out["batch"][n_dst] = torch.from_numpy(np.repeat(todo, nodes[todo])).to(dev)
-        for k in ("pe_attr", "peripheral_edge_attr", "peripheral_configuration_attr"):
-            if out[k] is not None:
-                out[k][n_dst] = host[k].to(dev)
-    return out, torch.from_numpy(status)
 
 
 # ------------------------------------------------------------------------------------------------ the rd projection

@@ -97,7 +97,7 @@ def kernel_ms(nptr, eptr, ei, dev, reps, workspace_bytes):
     """class name -> median milliseconds of its launch(es) alone, on resident tensors."""
     import numpy as np
     import torch
-    from kp_gnn_amd import _lib, ops
+    from kp_gnn_amd import _lib, ops, ops_dataset
     G, E = nptr.shape[0] - 1, int(eptr[-1])
     nodes = np.diff(nptr)
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)  # noqa: E731
@@ -110,7 +110,7 @@ def kernel_ms(nptr, eptr, ei, dev, reps, workspace_bytes):
         ids = np.flatnonzero(sel)
         if ids.size == 0:
             continue
-        runs = [(ids, 32 if cls == "wave" else 64, 0)] if cls != "large" else ops._rd_large_chunks(ids, nodes, slab, workspace_bytes)
+        runs = [(ids, 32 if cls == "wave" else 64, 0)] if cls != "large" else ops_dataset.workspace_runs(ids, nodes, slab, workspace_bytes)
         ws = torch.empty(max(8, max(r[2] for r in runs)), dtype=torch.uint8, device=dev)
         jobs = [(t(r[0], torch.int32), r[1], r[2]) for r in runs]
         go = lambda: [ops.count_labels_launch(G, nptr_d, eptr_d, ei_d, E, i, cap, out, st, ws, nb) for i, cap, nb in jobs]  # noqa: E731

@@ -152,19 +152,19 @@ def test_large_keyword_values_are_checked_before_anything_else():
 
 
 def test_runs_of_large_graphs_fit_the_workspace(built):
-    from kp_gnn_amd import _lib, ops
+    from kp_gnn_amd import _lib, ops_dataset
     slab = lambda cap: int(_lib.load().kpgnn_rd_large_workspace_bytes(cap, 1))  # noqa: E731
     nodes = np.array([5, 300, 129, 300, 40, 2048, 130, 257, 300, 300], dtype=np.int64)
     ids = np.flatnonzero(nodes > 128)
     for budget in (1, slab(300), 2 * slab(300), slab(2048), 1 << 30):
-        runs = ops._rd_large_chunks(ids, nodes, slab, budget)
+        runs = ops_dataset.workspace_runs(ids, nodes, slab, budget)
         assert np.concatenate([r[0] for r in runs]).tolist() == ids.tolist()          # every graph once, in call order
         for run_ids, cap, nbytes in runs:
             assert cap == int(nodes[run_ids].max()) and nbytes == len(run_ids) * slab(cap)
             assert nbytes <= budget or len(run_ids) == 1                                # a single graph always runs
-    assert len(ops._rd_large_chunks(ids, nodes, slab, 1)) == ids.size
-    assert len(ops._rd_large_chunks(ids, nodes, slab, 1 << 30)) == 1
-    one300 = ops._rd_large_chunks(ids, nodes, slab, slab(300))
+    assert len(ops_dataset.workspace_runs(ids, nodes, slab, 1)) == ids.size
+    assert len(ops_dataset.workspace_runs(ids, nodes, slab, 1 << 30)) == 1
+    one300 = ops_dataset.workspace_runs(ids, nodes, slab, slab(300))
     assert all(len(r[0]) == 1 for r in one300 if 300 in nodes[r[0]].tolist())           # never two 300-node graphs in a launch
 
 
