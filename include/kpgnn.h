@@ -1369,6 +1369,57 @@ int kpgnn_body_norm_fwd(const kpgnn_norm_desc* d, kpgnn_stream_t stream);
 int kpgnn_body_norm_bwd(const kpgnn_norm_desc* d, kpgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The same four norms PER GRAPH (csrc/body_norm_graph.hip): what PyG's modules compute when they ARE handed a batch vector.
+ * Graph g owns the contiguous rows [r0, r1), r0 = graph_ptr[g], r1 = min(graph_ptr[g+1], live), live = *n_dyn where given,
+ * else N, n = r1 - r0; the formulas above apply to those rows alone, with that n (+ residual[row,c] when given).  A graph with
+ * n <= 0 is skipped entirely; rows at or beyond `live`, and rows at or beyond graph_ptr[G], are never read, written or summed,
+ * in any output of either direction.
+ *   One team owns one graph from its statistics to its apply pass: a 64-lane wavefront where n < KPGNN_GRAPH_NORM_BLOCK_ROWS
+ *   (eight graphs per 512-thread block), a whole block from there on; the class is chosen by n alone.  A lane owns the columns
+ *   lane, lane + 64, ... whatever the alignment of the operands.  Every sum is taken in DOUBLE in an order fixed by the graph
+ *   alone (rows in row order per column - per wave, then the waves in order, for a block team - and the columns by one
+ *   butterfly), the coefficients stay in double, the apply pass is centred and done in double with contraction off, and the
+ *   result is rounded to fp32 once: THE BITS OF A GRAPH'S ROWS OF out AND gx DEPEND ON THAT GRAPH'S ROWS, C, kind, eps (weight,
+ *   bias, residual) AND ON NOTHING ELSE - not on G, the graph's position, the other graphs or the capacity N.  A constant
+ *   column and n == 1 give exact zeros (INSTANCE, PAIR); a constant block gives exactly bias (LAYER).
+ *   fwd: one launch.  `saved` (optional, float [G,4]) receives {mu, 1/(sd+eps), sd, n} (LAYER), {0, r, 0, n} (PAIR),
+ *        {0, 1/sqrt(n), 0, n} (GRAPHSIZE), {0, 0, 0, n} (INSTANCE) for the record; a skipped graph's row is left alone.
+ *   bwd: one launch.  It does NOT read `saved`: it recomputes the statistics of x in double in the same pass that sums gout
+ *        and gout * x (the rows are read once either way), because coefficients rounded to fp32 cannot hold a two-row graph's
+ *        gradient - a difference of nearly equal terms - to the tolerance of a float64 reference.  Where LAYER's block is
+ *        constant (sd == 0) the term through the standard deviation is dropped (K = 0), as body_norm.hip does for a constant
+ *        batch.  LAYER's gweight / gbias, where given, are sums over the live rows of ALL graphs: every team leaves a double
+ *        partial [2][C] in `workspace` and ONE more launch adds them in a fixed order.  GRAPHSIZE reads gout alone.
+ * No atomics.  1 <= C <= 256 (KPGNN_EINVAL below, KPGNN_ELIMIT above); N == 0 or G == 0 launches nothing.  x (x_stride >= C)
+ * and graph_ptr must be non-NULL for every kind; `workspace` (kpgnn_graph_norm_workspace_bytes, 8-byte aligned, need not be
+ * zeroed) is read by the LAYER backward with a gweight or gbias alone and may be NULL elsewhere.
+ * ---------------------------------------------------------------------------------------------- */
+#define KPGNN_GRAPH_NORM_BLOCK_ROWS 128     /* n >= this: a block per graph; below: a wavefront per graph */
+
+typedef struct kpgnn_graph_norm_desc {
+    int64_t N; int32_t C, kind; float eps;         /* rows (capacity with n_dyn), row width (1 .. 256), KPGNN_NORM_*, 1e-5 */
+    const float* x; int64_t x_stride;              /* device [N,C], row stride in floats (>= C); both directions */
+    const float* weight; const float* bias;        /* device [C]: LAYER (weight required, bias optional); NULL elsewhere */
+    const float* residual; int64_t res_stride;     /* optional device [N,C] added to out (fwd) */
+    float* out; int64_t out_stride;                /* device [N,C] (fwd) */
+    float* saved;                                  /* optional device float [G,4]: fwd out; bwd does not read it */
+    /* backward only */
+    const float* gout; int64_t gout_stride;        /* device [N,C] */
+    float* gx; int64_t gx_stride;                  /* device [N,C] */
+    float* gweight; float* gbias;                  /* device [C], optional (LAYER) */
+    void* workspace; size_t workspace_bytes;       /* >= kpgnn_graph_norm_workspace_bytes(N, G, C, kind) */
+    const int32_t* n_dyn;       /* optional live-row count (device int32[1], <= N; kpgnn_wgrad_desc explains); NULL: all N rows */
+    const int32_t* graph_ptr;                      /* device [G+1], non-decreasing */
+    int32_t G;
+} kpgnn_graph_norm_desc;
+
+/* 0 = the shape is not covered. */
+size_t kpgnn_graph_norm_saved_floats(int32_t G, int32_t C, int32_t kind);
+size_t kpgnn_graph_norm_workspace_bytes(int64_t N, int32_t G, int32_t C, int32_t kind);
+int kpgnn_graph_norm_fwd(const kpgnn_graph_norm_desc* d, kpgnn_stream_t stream);
+int kpgnn_graph_norm_bwd(const kpgnn_graph_norm_desc* d, kpgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Resistance-distance node feature (csrc/resistance.hip; data_utils.py:280-303, `--use_rd`).  For each graph g of
  * n = node_ptr[g+1] - node_ptr[g] nodes, with A the summed adjacency of its edges (ones; duplicates add, the diagonal is
  * ignored as scipy's csgraph.laplacian ignores it) and L+ the pseudo-inverse of the Laplacian D - A:

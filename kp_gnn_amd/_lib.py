@@ -380,6 +380,13 @@ class NormDesc(ctypes.Structure):
     ]
 
 
+GRAPH_NORM_BLOCK_ROWS = 128           # include/kpgnn.h KPGNN_GRAPH_NORM_BLOCK_ROWS: a block per graph from this many rows on
+
+
+class GraphNormDesc(ctypes.Structure):
+    _fields_ = NormDesc._fields_ + [("graph_ptr", c_vp), ("G", c_i32)]
+
+
 RD_OK, RD_ASYMMETRIC, RD_TOO_LARGE, RD_PIVOT, RD_RANGE = 0, 1, 2, 3, 4    # include/kpgnn.h KPGNN_RD_*
 RD_MAX_NODES, RD_WAVE_NODES = 128, 32                                   # KPGNN_RD_MAX_NODES, KPGNN_RD_WAVE_NODES
 RD_PROJ_MAX_H = 256                                                     # csrc/rd_proj.hip kMaxH
@@ -592,6 +599,10 @@ SIGNATURES = {
     "kpgnn_body_norm_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i32]),
     "kpgnn_body_norm_fwd": (ctypes.c_int, [ctypes.POINTER(NormDesc), c_vp]),
     "kpgnn_body_norm_bwd": (ctypes.c_int, [ctypes.POINTER(NormDesc), c_vp]),
+    "kpgnn_graph_norm_saved_floats": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
+    "kpgnn_graph_norm_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i32, c_i32, c_i32]),
+    "kpgnn_graph_norm_fwd": (ctypes.c_int, [ctypes.POINTER(GraphNormDesc), c_vp]),
+    "kpgnn_graph_norm_bwd": (ctypes.c_int, [ctypes.POINTER(GraphNormDesc), c_vp]),
     "kpgnn_attn_pool_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "kpgnn_attn_pool_fwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),
     "kpgnn_attn_pool_bwd": (ctypes.c_int, [ctypes.POINTER(AttnPoolDesc), c_vp]),

@@ -8,7 +8,8 @@ tests need a caller of their own: this file.  It keeps the reference's construct
 state_dict key names (so reference checkpoints and the golden bodies load verbatim) but shares one base
 class instead of three near-identical copies.  All five norm_type choices of the reference are built: "Batch" on the
 BatchNorm kernels, "Layer", "Instance", "GraphSize" and "Pair" on ops.body_norm (PyG's modules as the bodies call them: without
-a batch vector, the whole batch one graph).
+a batch vector, the whole batch one graph).  One argument the reference does not have: norm_scope="graph" hands those four
+the batch vector, so that every graph is normalised over its own rows; the default "batch" is the reference's behaviour.
 """
 import copy
 
@@ -235,7 +236,8 @@ class BatchNorm(nn.Module):
     def reset_parameters(self):
         self.module.reset_parameters()
 
-    def forward(self, x, residual=None):
+    def forward(self, x, residual=None, batch=None, num_graphs=None):
+        # (batch / num_graphs: accepted as the other norms take them and ignored - BatchNorm's statistics are the batch's)
         return batch_norm_act(x, self.module, relu=False, residual=residual)
 
 
@@ -254,8 +256,8 @@ class LayerNorm(nn.Module):
         nn.init.ones_(self.weight)
         nn.init.zeros_(self.bias)
 
-    def forward(self, x, residual=None):
-        return body_norm(x, "Layer", self.weight, self.bias, residual=residual, eps=self.eps)
+    def forward(self, x, residual=None, batch=None, num_graphs=None):
+        return body_norm(x, "Layer", self.weight, self.bias, residual=residual, eps=self.eps, batch=batch, num_graphs=num_graphs)
 
 
 class InstanceNorm(nn.Module):
@@ -269,8 +271,8 @@ class InstanceNorm(nn.Module):
     def reset_parameters(self):
         pass
 
-    def forward(self, x, residual=None):
-        return body_norm(x, "Instance", residual=residual, eps=self.eps)
+    def forward(self, x, residual=None, batch=None, num_graphs=None):
+        return body_norm(x, "Instance", residual=residual, eps=self.eps, batch=batch, num_graphs=num_graphs)
 
 
 class GraphSizeNorm(nn.Module):
@@ -279,8 +281,8 @@ class GraphSizeNorm(nn.Module):
     def reset_parameters(self):
         pass
 
-    def forward(self, x, residual=None):
-        return body_norm(x, "GraphSize", residual=residual)
+    def forward(self, x, residual=None, batch=None, num_graphs=None):
+        return body_norm(x, "GraphSize", residual=residual, batch=batch, num_graphs=num_graphs)
 
 
 class PairNorm(nn.Module):
@@ -293,8 +295,8 @@ class PairNorm(nn.Module):
     def reset_parameters(self):
         pass
 
-    def forward(self, x, residual=None):
-        return body_norm(x, "Pair", residual=residual, eps=self.eps)
+    def forward(self, x, residual=None, batch=None, num_graphs=None):
+        return body_norm(x, "Pair", residual=residual, eps=self.eps, batch=batch, num_graphs=num_graphs)
 
 
 def _make_norm(norm_type, hidden_size):
@@ -328,8 +330,13 @@ class _KHopBody(nn.Module):
 
     def __init__(self, num_layer, hidden_size, K, width, gate, init_emb, num_hop1_edge, max_edge_count, max_hop_num,
                  max_distance_count, JK, norm_type, virtual_node, residual, use_rd, wo_peripheral_edge,
-                 wo_peripheral_configuration, drop_prob):
+                 wo_peripheral_configuration, drop_prob, norm_scope="batch"):
         super().__init__()
+        if norm_scope not in ("batch", "graph"):
+            raise ValueError(f"norm_scope must be 'batch' or 'graph', got {norm_scope!r}")
+        # "batch": the reference's behaviour - its bodies hand the norms no batch vector, so the collated batch is one graph;
+        # "graph": every graph on its own rows (ops.body_norm with a batch vector).  Not a parameter: state_dict does not hold it.
+        self.norm_scope = norm_scope
         self.num_layer, self.hidden_size, self.K = num_layer, hidden_size, K
         self._periph_width, self._gate = width, gate
         self.dropout = nn.Dropout(drop_prob)
@@ -376,6 +383,15 @@ class _KHopBody(nn.Module):
             nn.init.normal_(self.pcw)
 
     # -- pieces of forward
+    def _norm_kw(self, data, batch):
+        """What every self.norms[l] call is handed besides its rows: nothing under norm_scope "batch", the batch vector and the
+        graph count the heads resolve under "graph"."""
+        if self.norm_scope != "graph":
+            return {}
+        if batch is None:
+            raise ValueError("norm_scope='graph' needs data.batch")
+        return {"batch": batch, "num_graphs": _num_graphs(batch, _get(data, "num_graphs"))}
+
     def _inputs(self, data):
         x = self.init_proj(data).squeeze()
         rd = _get(data, "rd")
@@ -519,10 +535,10 @@ class GNN(_KHopBody):
 
     def __init__(self, num_layer, gnn_layer, init_emb, num_hop1_edge, max_edge_count, max_hop_num, max_distance_count,
                  JK="last", norm_type="batch", virtual_node=True, residual=False, use_rd=False,
-                 wo_peripheral_edge=False, wo_peripheral_configuration=False, drop_prob=0.1):
+                 wo_peripheral_edge=False, wo_peripheral_configuration=False, drop_prob=0.1, norm_scope="batch"):
         super().__init__(num_layer, gnn_layer.output_size, gnn_layer.K, gnn_layer.output_dk, torch.sigmoid, init_emb,
                          num_hop1_edge, max_edge_count, max_hop_num, max_distance_count, JK, norm_type, virtual_node,
-                         residual, use_rd, wo_peripheral_edge, wo_peripheral_configuration, drop_prob)
+                         residual, use_rd, wo_peripheral_edge, wo_peripheral_configuration, drop_prob, norm_scope)
         self.output_dk = gnn_layer.output_dk
         self.gnns = nn.ModuleList(copy.deepcopy(gnn_layer) for _ in range(num_layer))
         self.reset_parameters()
@@ -539,6 +555,7 @@ class GNN(_KHopBody):
         _prepare_splits(self.gnns, x)
         periph = self._peripheral(data, x.size(0), x)
         vn, vn_pool = (self._vn_init(data, batch), None) if self.virtual_node else (None, None)
+        nkw = self._norm_kw(data, batch)
         h_list = [x]
         for l in range(self.num_layer):
             if self.virtual_node:
@@ -551,7 +568,7 @@ class GNN(_KHopBody):
             if h_list[l].is_cuda:
                 h_list[l]._kp_last_reader = self.gnns[l]
             h = self.norms[l](self.gnns[l](h_list[l], edge_index, edge_attr, pe_attr, periph),
-                              residual=h_list[l] if fuse_res else None)
+                              residual=h_list[l] if fuse_res else None, **nkw)
             res = h_list[l] if self.residual and not fuse_res else None
             if l != self.num_layer - 1:
                 h = self._drop(h, res)           # (with a mask between norm and residual, the add rides in the dropout launch)
@@ -569,12 +586,12 @@ class GNNPlus(_KHopBody):
 
     def __init__(self, num_layer, gnn_layer, init_emb, num_hop1_edge, max_edge_count, max_hop_num, max_distance_count,
                  JK="last", norm_type="batch", virtual_node=True, residual=False, use_rd=False,
-                 wo_peripheral_edge=False, wo_peripheral_configuration=False, drop_prob=0.1):
+                 wo_peripheral_edge=False, wo_peripheral_configuration=False, drop_prob=0.1, norm_scope="batch"):
         hidden, K = gnn_layer[-1].output_size, gnn_layer[-1].K
         assert num_layer >= K
         super().__init__(num_layer, hidden, K, hidden, torch.tanh, init_emb, num_hop1_edge, max_edge_count, max_hop_num,
                          max_distance_count, JK, norm_type, virtual_node, residual, use_rd, wo_peripheral_edge,
-                         wo_peripheral_configuration, drop_prob)
+                         wo_peripheral_configuration, drop_prob, norm_scope)
         self.gnns = nn.ModuleList(gnn_layer)
         for g in self.gnns:
             g._kp_emit_out_stats = True      # norms[l] follows every layer: its statistics come out of the layer's last kernel
@@ -592,6 +609,7 @@ class GNNPlus(_KHopBody):
         _prepare_splits(self.gnns, x)
         periph = self._peripheral(data, x.size(0), x)
         vn, vn_pool = (self._vn_init(data, batch), None) if self.virtual_node else (None, None)
+        nkw = self._norm_kw(data, batch)
         h_list, last_h = [x], x
         for l in range(self.num_layer):
             if self.virtual_node:
@@ -609,10 +627,10 @@ class GNNPlus(_KHopBody):
                 h = self.gnns[l].forward_slots(slots, edge_index, edge_attr[:, :k], pek, periph[:, :k], history=True,
                                                post_norm=post)
                 if post is None:
-                    h = norm(h, residual=res)
+                    h = norm(h, residual=res, **nkw)
             else:
                 h = self.gnns[l](torch.stack(slots, dim=1), edge_index, edge_attr[:, :k], pek, periph[:, :k])
-                h = self.norms[l](h, residual=res)   # norm (+ residual) in one pass
+                h = self.norms[l](h, residual=res, **nkw)   # norm (+ residual) in one pass
             res = last_h if self.residual and not fuse_res else None
             if l != self.num_layer - 1:
                 h = self._drop(h, res)
@@ -632,12 +650,12 @@ class GNNPrime(_KHopBody):
 
     def __init__(self, num_layer, gnn_layer, init_emb, num_hop1_edge, max_edge_count, max_hop_num, max_distance_count,
                  num_l1_layer=1, JK="last", norm_type="batch", virtual_node=True, residual=False, use_rd=False,
-                 wo_peripheral_edge=False, wo_peripheral_configuration=False, drop_prob=0.1):
+                 wo_peripheral_edge=False, wo_peripheral_configuration=False, drop_prob=0.1, norm_scope="batch"):
         assert num_l1_layer > 0
         assert num_layer >= 2
         super().__init__(num_layer, gnn_layer.output_size, gnn_layer.K, gnn_layer.output_dk, torch.sigmoid, init_emb,
                          num_hop1_edge, max_edge_count, max_hop_num, max_distance_count, JK, norm_type, virtual_node,
-                         residual, use_rd, wo_peripheral_edge, wo_peripheral_configuration, drop_prob)
+                         residual, use_rd, wo_peripheral_edge, wo_peripheral_configuration, drop_prob, norm_scope)
         self.output_dk = gnn_layer.output_dk
         self.num_l1_layer, self.num_l2_layer = num_l1_layer, num_layer - num_l1_layer
         self.khop_gnns = nn.ModuleList(copy.deepcopy(gnn_layer) for _ in range(num_l1_layer))
@@ -659,6 +677,7 @@ class GNNPrime(_KHopBody):
         _prepare_splits(list(self.khop_gnns) + list(self.gins), x)
         periph = self._peripheral(data, x.size(0), x)
         vn, vn_pool = (self._vn_init(data, batch), None) if self.virtual_node else (None, None)
+        nkw = self._norm_kw(data, batch)
         h_list = [x]
         for l in range(self.num_layer):
             if self.virtual_node:
@@ -672,7 +691,7 @@ class GNNPrime(_KHopBody):
                 h = layer(h_list[l], edge_index, edge_attr[:, :1])
             drops = l < self.num_l1_layer or l != self.num_layer - 1   # (:659 drops out after every K-hop layer)
             fuse_res = self.residual and (self.dropout.p == 0.0 or not self.training or not drops)
-            h = self.norms[l](h, residual=h_list[l] if fuse_res else None)
+            h = self.norms[l](h, residual=h_list[l] if fuse_res else None, **nkw)
             res = h_list[l] if self.residual and not fuse_res else None
             if drops:
                 h = self._drop(h, res)

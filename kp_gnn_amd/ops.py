@@ -1990,7 +1990,9 @@ def jk_lstm_score(states, lstm):
 # ------------------------------------------------------------------------------------------------ the bodies' other norms
 # norm_type "Layer", "Instance", "GraphSize", "Pair" (models/GNNs.py:103-112; kpgnn.h, kpgnn_norm_desc): PyG's modules called
 # without a batch vector, so the whole batch is one graph.  None has running statistics (training and evaluation compute the
-# same), and what the backward keeps besides x is a float [2C + 4] of coefficients.
+# same), and what the backward keeps besides x is a float [2C + 4] of coefficients.  A caller that does pass a batch vector
+# (body_norm(..., batch=, num_graphs=); the bodies under norm_scope="graph") gets every graph normalised over its own rows:
+# kpgnn_graph_norm_desc, csrc/body_norm_graph.hip.
 NORM_KINDS = {"Layer": _lib.NORM_LAYER, "Instance": _lib.NORM_INSTANCE, "GraphSize": _lib.NORM_GRAPHSIZE, "Pair": _lib.NORM_PAIR}
 _NATIVE_NORMS = True
 # per kind, on EXACT-SHAPE batches: GraphSize is one framework launch per direction to begin with, and an eager step measured
@@ -2031,9 +2033,40 @@ def body_norm_applies(x):
     return bool(x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and 1 <= x.shape[1] <= _lib.NORM_MAX_C)
 
 
-def body_norm_reference(x, kind, weight=None, bias=None, residual=None, eps=1e-5):
+def _graph_norm_reference(x, kind, weight, bias, eps, batch, num_graphs):
+    """The four norms per graph of `batch` (int64 [N], graph ids in [0, num_graphs)) as index_add_ sums: no loop over graphs."""
+    C = x.shape[1]
+    cnt = torch.zeros(num_graphs, dtype=x.dtype, device=x.device).index_add_(0, batch, torch.ones_like(x[:, 0])).clamp(min=1)
+
+    def rows_sum(t):        # [N,C] -> [G,C]
+        return torch.zeros((num_graphs, C), dtype=x.dtype, device=x.device).index_add_(0, batch, t)
+
+    if kind == "GraphSize":
+        return x / cnt.sqrt()[batch].unsqueeze(1)
+    if kind == "Layer":
+        nc = (cnt * C).unsqueeze(1)
+        xc = x - (rows_sum(x).sum(1, keepdim=True) / nc)[batch]
+        var = rows_sum(xc * xc).sum(1, keepdim=True) / nc
+        pos = var > 0           # (a constant block: sd = 0 with a zero gradient, as torch.std has it, not sqrt's 0 * inf)
+        sd = torch.where(pos, var, torch.ones_like(var)).sqrt() * pos
+        return xc / (sd + eps)[batch] * weight + bias
+    xc = x - (rows_sum(x) / cnt.unsqueeze(1))[batch]
+    if kind == "Instance":
+        return xc / (rows_sum(xc * xc) / cnt.unsqueeze(1) + eps).sqrt()[batch]
+    return xc / (eps + rows_sum(xc * xc).sum(1, keepdim=True) / cnt.unsqueeze(1)).sqrt()[batch]      # Pair
+
+
+def body_norm_reference(x, kind, weight=None, bias=None, residual=None, eps=1e-5, *, batch=None, num_graphs=None):
     """The framework expression of the four norms (any device, any floating dtype): what PyG's LayerNorm (mode "graph"),
-    InstanceNorm (no affine, no running statistics), GraphSizeNorm and PairNorm (scale 1) compute without a batch vector."""
+    InstanceNorm (no affine, no running statistics), GraphSizeNorm and PairNorm (scale 1) compute without a batch vector - or,
+    with `batch` (sorted graph ids [N]) and `num_graphs`, per graph."""
+    if kind not in NORM_KINDS:
+        raise ValueError(f"norm kind must be one of {sorted(NORM_KINDS)}, got {kind!r}")
+    if batch is not None:
+        if num_graphs is None:
+            raise ValueError("body_norm: a batch vector needs num_graphs")
+        y = _graph_norm_reference(x, kind, weight, bias, eps, batch, int(num_graphs))
+        return y if residual is None else y + residual
     if kind == "Layer":
         xc = x - x.mean()
         y = xc / (xc.std(unbiased=False) + eps) * weight + bias
@@ -2117,9 +2150,86 @@ class BodyNorm(torch.autograd.Function):
         return (gx if need_x else None, gw if need_w else None, gb if need_b else None, gout if need_r else None, None, None)
 
 
-def body_norm(x, kind, weight=None, bias=None, residual=None, eps=1e-5):
-    """The Layer / Instance / GraphSize / Pair norm of the bodies over the rows x [N,C] (+ residual), the whole batch as one
-    graph; weight / bias [C] go with "Layer" and with no other kind.  Where body_norm_applies and the switch is on
+def _graph_norm_desc(x, kind, eps, ptr, num_graphs):
+    N, C = x.shape
+    d = _lib.GraphNormDesc()
+    d.N, d.C, d.kind, d.eps = N, C, NORM_KINDS[kind], eps
+    d.x, d.x_stride = x.data_ptr(), x.stride(0)
+    d.graph_ptr, d.G = ptr.data_ptr(), num_graphs
+    d.n_dyn = dyn_ptr(N)
+    return d
+
+
+def _graph_norm_fwd_launch(x, kind, weight, bias, residual, eps, ptr, num_graphs):
+    """(out, x as the kernel reads it): one kpgnn_graph_norm_fwd call."""
+    N, C = x.shape
+    x = _rows_view(x, C)
+    out = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    d = _graph_norm_desc(x, kind, eps, ptr, num_graphs)
+    d.out, d.out_stride = out.data_ptr(), C
+    if kind == "Layer":
+        weight, bias = weight.contiguous(), bias.contiguous()
+        d.weight, d.bias = weight.data_ptr(), bias.data_ptr()
+    if residual is not None:
+        residual = _rows_view(residual, C)
+        d.residual, d.res_stride = residual.data_ptr(), residual.stride(0)
+    _lib.launch("kpgnn_graph_norm_fwd", x.device, ctypes.byref(d))
+    return out, x
+
+
+class GraphBodyNorm(torch.autograd.Function):
+    """out = norm per graph (x) (+ residual): one kpgnn_graph_norm_fwd call forward, one kpgnn_graph_norm_bwd call backward.
+    Saves x (not for GraphSize), the graph pointer and Layer's weight - the backward recomputes the statistics (kpgnn.h says
+    why); the residual's gradient is the incoming one."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, kind, eps, ptr, num_graphs):
+        out, x = _graph_norm_fwd_launch(x, kind, weight, bias, residual, eps, ptr, num_graphs)
+        ctx.save_for_backward(ptr, *(() if kind == "GraphSize" else (x,)), *(() if weight is None else (weight,)))
+        ctx.kind, ctx.eps, ctx.num_graphs = kind, eps, num_graphs
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        N, C = gout.shape
+        gout_rows = _rows_view(gout, C)
+        if ctx.kind == "GraphSize":
+            (ptr,), x, w = ctx.saved_tensors, gout_rows, []     # (the descriptor wants some x; this kind never reads it)
+        else:
+            ptr, x, *w = ctx.saved_tensors
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        gx = gw = gb = None
+        if need_x or need_w or need_b:
+            d = _graph_norm_desc(x, ctx.kind, ctx.eps, ptr, ctx.num_graphs)
+            # (rows beyond the live count of a dynamic_rows block are never written: whoever reads gx there skips them too)
+            gx = torch.empty((N, C), dtype=torch.float32, device=x.device)
+            d.gout, d.gout_stride, d.gx, d.gx_stride = gout_rows.data_ptr(), gout_rows.stride(0), gx.data_ptr(), C
+            ws = None
+            if w:
+                weight = w[0].contiguous()
+                d.weight = weight.data_ptr()
+                if need_w or need_b:
+                    gw, gb = torch.empty_like(weight), torch.empty_like(weight)
+                    nbytes = _lib.load().kpgnn_graph_norm_workspace_bytes(N, ctx.num_graphs, C, d.kind)
+                    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+                    d.gweight, d.gbias, d.workspace, d.workspace_bytes = gw.data_ptr(), gb.data_ptr(), ws.data_ptr(), nbytes
+            _lib.launch("kpgnn_graph_norm_bwd", x.device, ctypes.byref(d))
+            del ws
+        return (gx if need_x else None, gw if need_w else None, gb if need_b else None, gout if need_r else None,
+                None, None, None, None)
+
+
+def body_norm(x, kind, weight=None, bias=None, residual=None, eps=1e-5, *, batch=None, num_graphs=None):
+    """The Layer / Instance / GraphSize / Pair norm of the bodies over the rows x [N,C] (+ residual); weight / bias [C] go with
+    "Layer" and with no other kind.
+
+    With `batch` (the sorted graph ids [N] of a collated batch) and `num_graphs` every graph is normalised on its own rows
+    (kpgnn.h, kpgnn_graph_norm_desc): a graph's result does not depend on what else is in the batch.  Where body_norm_applies and
+    set_native_norms is on - every kind, exact-shape batches included - that is one kpgnn_graph_norm_fwd call and one
+    kpgnn_graph_norm_bwd call; graph_ptr_of(batch, num_graphs) supplies the pointer, so the batch vector needs one eager use
+    before a capture.  Everything else keeps the framework expression (body_norm_reference), which has no dynamic row count.
+
+    Without `batch` the whole batch is one graph, as the reference's bodies have it.  Where body_norm_applies and the switch is on
     (set_native_norms; "GraphSize" on exact-shape batches only after set_native_norm_exact("GraphSize", True), inside a dynamic_rows
     block always), one kpgnn_body_norm_fwd call and one kpgnn_body_norm_bwd call - the statistics are over the LIVE rows of
     a dynamic_rows block, and rows beyond them are left alone; under no_grad, or when nothing requires a gradient, no autograd
@@ -2129,15 +2239,26 @@ def body_norm(x, kind, weight=None, bias=None, residual=None, eps=1e-5):
         raise ValueError(f"norm kind must be one of {sorted(NORM_KINDS)}, got {kind!r}")
     if (kind == "Layer") != (weight is not None and bias is not None) or (kind != "Layer" and (weight is not None or bias is not None)):
         raise ValueError("body_norm: weight and bias go with kind 'Layer' and with no other")
-    native = _NATIVE_NORMS and body_norm_applies(x) and (_NATIVE_NORM_EXACT[kind] or dyn_ptr(x.shape[0]) is not None)
+    per_graph = batch is not None
+    if per_graph and num_graphs is None:
+        raise ValueError("body_norm: a batch vector needs num_graphs")
+    native = _NATIVE_NORMS and body_norm_applies(x) and (per_graph or _NATIVE_NORM_EXACT[kind] or dyn_ptr(x.shape[0]) is not None)
     for t in (weight, bias):
         native = native and (t is None or (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (x.shape[1],)))
     native = native and (residual is None or (residual.is_cuda and residual.dtype == torch.float32 and residual.shape == x.shape))
     if not native:
         if x.dim() == 2:
             refuse_dynamic_rows(f"the framework expression of the {kind} norm", x.shape[0])
-        return body_norm_reference(x, kind, weight, bias, residual, eps)
+        return body_norm_reference(x, kind, weight, bias, residual, eps, batch=batch, num_graphs=num_graphs)
     eps = float(eps)
+    if per_graph:
+        num_graphs = int(num_graphs)
+        if batch.shape[0] != x.shape[0]:
+            raise ValueError(f"body_norm: batch names {batch.shape[0]} rows, x has {x.shape[0]}")
+        ptr = graph_ptr_of(batch, num_graphs)
+        if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (x, weight, bias, residual)):
+            return _graph_norm_fwd_launch(x.detach(), kind, weight, bias, residual, eps, ptr, num_graphs)[0]
+        return GraphBodyNorm.apply(x, weight, bias, residual, kind, eps, ptr, num_graphs)
     if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (x, weight, bias, residual)):
         return _norm_fwd_launch(x.detach(), kind, weight, bias, residual, eps)[0]      # no autograd node, nothing saved
     return BodyNorm.apply(x, weight, bias, residual, kind, eps)
