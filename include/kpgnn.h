@@ -210,7 +210,15 @@ enum { KPGNN_STORE_F32 = 0, KPGNN_STORE_BF16 = 1 };
 
 /* Arithmetic of the dense fp32 products that offer a choice.  AUTO: the bf16-split product where the kernel has one for the
  * shape - every fp32 operand is the exact sum of three bf16 pieces, the six leading piece products run on the bf16 matrix
- * cores with fp32 accumulation (dropped terms < 2^-24 of a product: the error of fp32 accumulation itself) - else F32.
+ * cores with fp32 accumulation - else F32.  The three dropped piece products sum to at most 7.83 * 2^-24 |a b| per product
+ * (reached when the low 16 mantissa bits of both operands are set; truncation gives them one sign, so they add up along a
+ * row): per element, |y - exact| <= the error of fp32 accumulation + 8 * 2^-24 * (sum_k |x_k| |w_k| + |bias|).
+ * Operand range: the bound holds for every finite operand down to pieces that are SUBNORMAL bf16 numbers - measured on
+ * gfx950 with x scaled by 2^-110 (values normal, their m and l pieces subnormal) against W scaled by 2^110: the split's packed
+ * subtracts and v_mfma_f32_32x32x16_bf16 keep subnormal inputs, the error is that of the unscaled product - and up to
+ * |x| = 2^126 with |w| <= 2^-20.  While no piece is subnormal, scaling x, w and bias by powers of two scales the result's bits
+ * exactly.  A row of x that holds an Inf or a NaN comes out non-finite and touches no other row (the ReLU of
+ * kpgnn_linear_group_fwd keeps a NaN, as torch.relu does).  tests/test_bf16_split_products.py holds all of this.
  * F32: v_mfma_f32_32x32x2_f32 always. */
 enum { KPGNN_MATH_AUTO = 0, KPGNN_MATH_F32 = 1 };
 

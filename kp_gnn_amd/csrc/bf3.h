@@ -2,9 +2,13 @@
 //
 // An fp32 value v is EXACTLY h + m + l with three bf16 pieces of 8 significant bits each, obtained by truncation:
 //     h = top 16 bits of v,   m = top 16 bits of (v - h),   l = v - h - m   (at most 8 significant bits are left: l is a bf16)
-// and for two such values  a b = ah bh + (ah bm + am bh) + (am bm + ah bl + al bh) + [three terms below 2^-24 |a b|: dropped]:
-// six exact bf16 products, accumulated in fp32 (smallest first), leave the rounding error of fp32 accumulation itself, at
-// 6/16 of the matrix time of v_mfma_f32_32x32x2_f32 (which runs at the vector rate).
+// and for two such values  a b = ah bh + (ah bm + am bh) + (am bm + ah bl + al bh) + [am bl + al bm + al bl: dropped]:
+// six exact bf16 products, accumulated in fp32 (smallest first), at 6/16 of the matrix time of v_mfma_f32_32x32x2_f32 (which
+// runs at the vector rate).  The dropped terms sum to at most 7.83 * 2^-24 |a b| (about 2^-21), reached when the low 16
+// mantissa bits of both operands are set (a = b = 0x3F80FFFF: m = 255 * 2^-15, l = 255 * 2^-23, 2 m l + l l = 7.95 * 2^-24
+// against a b = 1.0157); truncation makes them all of one sign, so over a row of such operands they add up instead of
+// averaging out.  Per element the result is within fp32 accumulation's own error plus 8 * 2^-24 sum_k |a_k b_k|
+// (tests/test_bf16_split_products.py holds every kernel to that; DESIGN.md has the measured figures).
 // Users: linear_bf3.hip (lin3_kernel: store_planes, mma6; lin3_wsplit*: split2 / pack), linear_bf3_fused.hip (lin3f_kernel:
 // store_planes, mma6), attention.hip (attn_scan_fwd_kernel, attn_dx_kernel: mma6, split2 / pack), wgrad.hip (wgrad3_kernel:
 // split2 / pack - it stages 8 ROWS of a column per item, and its six products run product by product over its TI column tiles,

@@ -178,6 +178,10 @@ int64_t agg_route_count(int bwd, int route);
 int agg_small_fwd(const kpgnn_agg_fwd_desc* d, hipStream_t s, bool* handled);
 int agg_small_bwd(const kpgnn_agg_bwd_desc* d, hipStream_t s, bool* handled);
 
+// ReLU that keeps a NaN, as torch.relu does: fmaxf(NaN, 0) is 0 (v_max_f32 returns the other operand), and a projection
+// that turns a diverged row into zeros hides it.  One compare and one select; -0 cannot reach it (accumulators start at +0).
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
+
 // erf(z) by Abramowitz-Stegun 7.1.26 (max abs error 5.4e-7 in fp32 over [-6,6]; exact +-1 beyond): ~14 VALU ops
 // against ~30 for libm's erff, which made the GELU epilogue VALU-bound (28 us of a 160 us launch).  Also
 // returns e2 = exp(-z*z), which the backward needs for the Gaussian density.

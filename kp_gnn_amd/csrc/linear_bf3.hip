@@ -4,8 +4,9 @@
 // Contract: include/kpgnn.h, kpgnn_linear_group_fwd / kpgnn_linear_fwd with math = KPGNN_MATH_AUTO and a workspace.
 //
 // The fp32 matrix instruction runs at 1/16 of the bf16 rate; an fp32 value is exactly h + m + l with three bf16 pieces (8 + 8 + 8
-// significant bits, split by truncation), and  a b = ah bh + (ah bm + am bh) + (am bm + ah bl + al bh) + [< 2^-24 |a b|]:
-// six exact products on v_mfma_f32_32x32x16_bf16, fp32 accumulation, smallest first (bf3.h; the weight gradient: wgrad.hip).
+// significant bits, split by truncation), and  a b = ah bh + (ah bm + am bh) + (am bm + ah bl + al bh) + [<= 7.83 * 2^-24 |a b|,
+// reached when both operands' low 16 mantissa bits are set]: six exact products on v_mfma_f32_32x32x16_bf16, fp32 accumulation,
+// smallest first (bf3.h; the weight gradient: wgrad.hip).
 //
 // Two launches.  (1) W is split ONCE into the matrix instruction's B-fragment layout ([state][32-column strip][k step][piece]
 // [lane] x 16 bytes, <= 1 MB, L2-resident): every block needs all of it, and splitting a strip per block and state cost the
@@ -207,7 +208,7 @@ lin3_kernel(const L3Params p) {
 #pragma unroll
                 for (int v = 0; v < 16; ++v) {
                     float val = acc[m][v] + b;
-                    if (relu) val = fmaxf(val, 0.f);
+                    if (relu) val = relu_keep_nan(val);
                     *reinterpret_cast<float*>(base + off) = val;
                     off += (v & 3) == 3 ? row5 : row1;
                 }
@@ -217,7 +218,7 @@ lin3_kernel(const L3Params p) {
 #pragma unroll
                 for (int v = 0; v < 16; ++v) {
                     float val = acc[m][v] + b;
-                    if (relu) val = fmaxf(val, 0.f);
+                    if (relu) val = relu_keep_nan(val);
                     if (32 * m + (v & 3) + 8 * (v >> 2) < lane_rows) *reinterpret_cast<float*>(base + off) = val;
                     off += (v & 3) == 3 ? row5 : row1;
                 }

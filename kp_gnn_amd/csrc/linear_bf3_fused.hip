@@ -1,7 +1,8 @@
 // The MLPs' Linear + BatchNorm launches (lin_fused.h: y = f(x) W^T + b with BatchNorm work folded into the load and store phases)
 // on the bf16 matrix cores through exact three-way bf16 splits (bf3.h; skeleton: linear_bf3.hip).  gfx950.
 // Contract: include/kpgnn.h, kpgnn_linear_bn with math = KPGNN_MATH_AUTO and a workspace; same PRO / EPI semantics, same
-// statistics slots as lin_fused_kernel, which stays the path for small batches and for KPGNN_MATH_F32.
+// statistics slots as lin_fused_kernel, which stays the path for small batches and for KPGNN_MATH_F32.  Six of the nine piece
+// products are kept; the dropped three are at most 7.83 * 2^-24 |a b| per product (both operands' low 16 mantissa bits set).
 //
 // A block of 8 waves works through groups of 32 rows (blocks = CUs, ~6 groups each at the bench shape).  Waves 4-7 stage: the
 // prologue arithmetic of PRO 1 / 2 / 3 happens on the float4 they fetched (PRO >= 2: two source tensors, the transformed rows

@@ -131,7 +131,7 @@ linear_group_kernel(const LgParams p) {
                     const int64_t r = r0 + m * 32 + c;
                     if (r < N) {
                         float4 v = make_float4(acc[m][4 * g] + bb.x, acc[m][4 * g + 1] + bb.y, acc[m][4 * g + 2] + bb.z, acc[m][4 * g + 3] + bb.w);
-                        if (p.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                        if (p.relu) { v.x = relu_keep_nan(v.x); v.y = relu_keep_nan(v.y); v.z = relu_keep_nan(v.z); v.w = relu_keep_nan(v.w); }
                         *reinterpret_cast<float4*>(p.y + r * O + ob) = v;
                     }
                 }

@@ -375,9 +375,9 @@ wgrad2_kernel(const Wg2Args A) {
 // The fp32 matrix instruction above runs at 1/16 of the bf16 rate and the chip holds ~1.6 GHz under it: the kernel sits at
 // 65-85 TFLOP/s, twice its operand time from HBM.  An fp32 value is EXACTLY the sum of three bf16 pieces (8 + 8 + 8 significant
 // bits, split by truncation: h = top 16 bits of v, m = top 16 bits of v - h, l = v - h - m), so
-//     a b = ah bh + (ah bm + am bh) + (am bm + ah bl + al bh) + [three terms below 2^-24 |a b|: dropped]:
+//     a b = ah bh + (ah bm + am bh) + (am bm + ah bl + al bh) + [three terms, <= 7.83 * 2^-24 |a b| together: dropped; bf3.h]:
 // six exact bf16 products per k on v_mfma_f32_32x32x16_bf16 with fp32 accumulation - 6/16 of the matrix time of the fp32
-// instruction for the rounding error of fp32 accumulation itself (smallest terms first within a k step).  The bf16 instruction wants 8 consecutive k (= rows) of one column per lane, so the
+// instruction (smallest terms first within a k step).  The bf16 instruction wants 8 consecutive k (= rows) of one column per lane, so the
 // chunk is staged COLUMN-major: a thread fetches 8 rows x 4 columns (8 float4 requests, a chunk ahead), splits them and
 // writes 4 x 3 packed 16-byte items; 80-byte column pitch = conflict-free 16-byte reads.
 constexpr int kW3Pitch = 40;      // bf16 per staged column: 32 rows + 8 of padding

@@ -9,7 +9,7 @@
 // The fp32 matrix instructions (v_mfma_f32_32x32x2_f32) run at the VECTOR rate - 1/16 of the bf16 ones - and the chip holds
 // only ~1.6 GHz under them: every dense kernel of the KP-GIN+ step sits at 45-85 TFLOP/s whatever its structure (the BLAS
 // library's own fp32 GEMM: 76).  An fp32 value is the exact sum of three bf16 pieces (hi + mid + lo = 24 mantissa bits), so
-//     a * b = ah*bh + (ah*bm + am*bh) + (am*bm + ah*bl + al*bh) + [terms below 2^-24 of the product: dropped],
+//     a * b = ah*bh + (ah*bm + am*bh) + (am*bm + ah*bl + al*bh) + [three terms, <= 7.83 * 2^-24 of the product together: dropped],
 // six bf16 products with fp32 accumulation, smallest first: 6/16 of the matrix-core time of the fp32 instruction for an error
 // of the order of fp32 rounding itself (the products are exact, the sum is the usual fp32 accumulation).
 #include "kpgnn_common.h"
