@@ -695,6 +695,13 @@ int kpgnn_linear_wgrad(const kpgnn_wgrad_desc* d, kpgnn_stream_t stream);
 /* Two weight gradients with the same (O, I) in ONE launch + one ordered reduction (the two Linears of a
  * Linear-BatchNorm-ReLU x2 MLP): workspace >= 2 * kpgnn_wgrad_workspace_bytes(O, I), taken from a. */
 int kpgnn_linear_wgrad_pair(const kpgnn_wgrad_desc* a, const kpgnn_wgrad_desc* b, kpgnn_stream_t stream);
+/* `count` such pairs (2 * count <= 16) that share N, n_dyn, O and I, in ONE launch of the bf16-split kernel: the weight
+ * gradients of all the MLPs of a backward pass, which nothing reads before the pass ends.  a[p] / b[p] (HOST arrays of
+ * descriptors) are what kpgnn_linear_wgrad_pair takes, each pair with its own workspace and its own a[p]->defer job; every
+ * pair keeps the slicing of a launch of its own, so dw / db are bit for bit what kpgnn_linear_wgrad_pair gives.  Pairs the
+ * bf16-split kernel does not take (KPGNN_MATH_F32, O or I > 128, unaligned operands, mixed shapes) run as `count` pair calls. */
+int kpgnn_linear_wgrad_many(const kpgnn_wgrad_desc* const* a, const kpgnn_wgrad_desc* const* b, int32_t count,
+                            kpgnn_stream_t stream);
 /* Grouped-K weight gradient: the Linear's input was the CONCATENATION of `group` (<= 16) states x_l [N,I] that live in
  * separate tensors (the bodies' jumping-knowledge projection, models/GNNs.py:216-218 / :455-457: cat(h_list) -> Linear):
  * dw [O, group*I] with dw[:, l*I:(l+1)*I] = dy^T x_l, db = sum dy.  d->x is ignored (x_group is a HOST array of device

@@ -558,6 +558,8 @@ SIGNATURES = {
     "kpgnn_wgrad_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "kpgnn_linear_wgrad": (ctypes.c_int, [ctypes.POINTER(WgradDesc), c_vp]),
     "kpgnn_linear_wgrad_pair": (ctypes.c_int, [ctypes.POINTER(WgradDesc), ctypes.POINTER(WgradDesc), c_vp]),
+    "kpgnn_linear_wgrad_many": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(WgradDesc)), ctypes.POINTER(ctypes.POINTER(WgradDesc)),
+                                               c_i32, c_vp]),
     "kpgnn_wgrad_group_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "kpgnn_linear_wgrad_group": (ctypes.c_int, [ctypes.POINTER(WgradDesc), c_vp, c_i32, c_vp]),
     "kpgnn_linear_bn": (ctypes.c_int, [ctypes.POINTER(LinearBnDesc), c_vp]),

@@ -246,11 +246,13 @@ struct Wg2Prob {
     const float* xm; const float* xi; const float* xg; const float* xb;
     int xrelu;
     int64_t dys, xs, out_off, bias_off;      // offsets inside a slab row; bias_off < 0: this problem writes no bias gradient
+    float* slab;                             // this problem's slab (the problems of one call share it; kpgnn_linear_wgrad_many: one per pair)
 };
 struct Wg2Args {
     int64_t N; const int32_t* n_dyn;
     int O, I, nprob; int64_t ldw;
-    float* slab; int64_t slab_row;
+    int64_t slab_row;
+    int nslices;                             // slab rows per problem (wgrad3_kernel; wgrad2_kernel runs a block per slice)
     Wg2Prob q[kW2MaxProb];
 };
 
@@ -359,7 +361,7 @@ wgrad2_kernel(const Wg2Args A) {
         __syncthreads();
     }
     bsum += __shfl_xor(bsum, 32);                     // the two k halves hold different rows of the same column
-    float* out = A.slab + (int64_t)slice * A.slab_row;
+    float* out = q.slab + (int64_t)slice * A.slab_row;
 #pragma unroll
     for (int t = 0; t < TI; ++t) {
         const int i = t * 32 + c;
@@ -399,12 +401,14 @@ wgrad3_kernel(const Wg2Args A) {
     const int O = A.O, I = A.I;
     const int bufsz = 3 * (O + I) * P;                     // bf16 items per buffer: [3][O][P] pieces of dy, then [3][I][P] of x
     __bf16* pl = reinterpret_cast<__bf16*>(w2);
-    float* coef = reinterpret_cast<float*>(pl + 2 * bufsz);   // [4][I] x transform; afterwards [4][O] bias partials
+    float* coef = reinterpret_cast<float*>(pl + 2 * bufsz);   // [4][I] x transform
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (scalar: the role tests below become scalar branches)
     const int kg = lane >> 5, c = lane & 31;
     const int nprob = A.nprob;
-    const int pi = (int)(blockIdx.x % nprob), slice = (int)(blockIdx.x / nprob), nslices = (int)(gridDim.x / nprob);
+    // A block stays inside ONE problem (its x transform in LDS holds for the launch) and walks that problem's slices pb, pb + G,
+    // ...: G == nslices is a block per slice; kpgnn_linear_wgrad_many runs up to 16 problems on the chip's 256 blocks, G < nslices.
+    const int pi = (int)(blockIdx.x % nprob), pb = (int)(blockIdx.x / nprob), G = (int)(gridDim.x / nprob), nslices = A.nslices;
     Wg2Prob q = A.q[0];
 #pragma unroll
     for (int i = 1; i < kW2MaxProb; ++i)
@@ -414,7 +418,27 @@ wgrad3_kernel(const Wg2Args A) {
     if (tr)
         for (int i = tid; i < I; i += 512) { coef[i] = q.xm[i]; coef[I + i] = q.xi[i]; coef[2 * I + i] = q.xg[i]; coef[3 * I + i] = q.xb[i]; }
     const int64_t chunks = (N + R - 1) / R;
-    const int64_t mine = slice < chunks ? (chunks - slice + nslices - 1) / nslices : 0;     // chunks slice, slice + nslices, ...
+    // Slice s owns the chunks s, s + nslices, ...  The chunks of all the block's slices are walked as ONE sequence, `total` long:
+    // the requests never drain at a slice boundary.
+    const int nch = (int)chunks;
+    const int slim = min(nslices, nch);                            // slices with at least one chunk
+    const int nv = (nslices - pb + G - 1) / G;                     // slices of this block ...
+    const int nfull = pb < slim ? (slim - pb + G - 1) / G : 0;     // ... of which with a chunk (the first ones)
+    int total = 0;
+    {
+        const int m = (nch + nslices - 1) / nslices, rem = nch - (m - 1) * nslices;      // m chunks below slice `rem`, then m - 1
+        const int nm = pb < rem ? (rem - pb + G - 1) / G : 0;
+        total = nch > 0 ? nv * (m - 1) + nm : 0;
+    }
+    // Position in that sequence (all scalar): chunk c of slice s; past the block's last chunk it stays there.
+    struct Cur { int s, c; };
+    auto ends = [&](const Cur& cu) { return cu.c + nslices >= nch; };      // the slice's last chunk
+    auto step = [&](Cur& cu) {
+        const bool wrap = ends(cu), go = wrap && cu.s + G < slim;
+        cu.s = go ? cu.s + G : cu.s;
+        cu.c = wrap ? (go ? cu.s : cu.c) : cu.c + nslices;
+    };
+    const Cur first = {pb, pb};
     const bool producer = wave >= 4;
     // ---- staging task of a producer thread, fixed for the launch: (row group of 8, 4 columns) of dy (waves 4-5) or x (6-7)
     const bool is_x = wave >= 6;
@@ -430,15 +454,33 @@ wgrad3_kernel(const Wg2Args A) {
     const bool xform = tr && is_x;
     const int64_t last = N - 1;
     bf3_f2 bs01 = {0.f, 0.f}, bs23 = {0.f, 0.f};            // dy tasks: column sums of this thread's rows (the bias gradient)
+    // A slice's bias partials: the four row groups of a column group sit in four neighbouring lanes and are added in row-group
+    // order, (g0 + g1) + (g2 + g3); the sums start over for the block's next slice.
+    auto bias_out = [&](int s) {
+        float b4[4] = {bs01.x, bs01.y, bs23.x, bs23.y};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            b4[e] += __shfl_xor(b4[e], 1);
+            b4[e] += __shfl_xor(b4[e], 2);
+        }
+        if (q.bias_off >= 0 && owner && g == 0) {
+            float* bo = q.slab + (int64_t)s * A.slab_row + q.bias_off + 4 * cg;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bo[e] = b4[e];
+        }
+        bs01 = bf3_f2{0.f, 0.f}; bs23 = bf3_f2{0.f, 0.f};
+    };
     // The staging loop, instantiated per role (M: this wave applies the ReLU mask to what it stages, i.e. it stages dy and there is one).
     auto produce = [&](auto mask_c) {
         constexpr bool M = decltype(mask_c)::value;
         float4 pv0[8], pm0[8], pv1[8], pm1[8];
+        Cur ic = first, cc = first;        // the next chunk to request / to stage
         // Requests are unconditional in every respect - clamped rows, clamped chunk index, no branch on the role or the mask: the
         // compiler then knows how many requests are in flight at each use and waits for exactly the oldest (one `if` around an
         // issue and it must assume the younger set was never requested: vmcnt(7) at the first use, i.e. a wait for both sets).
-        auto issue = [&](int64_t k, float4 (&pv)[8], float4 (&pm)[8]) {
-            const int64_t c0 = (slice + min(k, mine - 1) * nslices) * R;          // (scalar)
+        auto issue = [&](float4 (&pv)[8], float4 (&pm)[8]) {
+            const int64_t c0 = (int64_t)ic.c * R;               // (scalar)
+            step(ic);
             const float* cp = src + c0 * sstride;                                  // (scalar) the chunk's first row
             const float* mp = M ? q.mask + c0 * sstride : nullptr;
             const int lim = (int)min((int64_t)R, N - c0) - 1;                     // (scalar) last valid row of the chunk
@@ -450,8 +492,8 @@ wgrad3_kernel(const Wg2Args A) {
                 if (M) pm[j] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(mp) + off);
             }
         };
-        auto commit = [&](int64_t k, float4 (&pv)[8], float4 (&pm)[8]) {       // (k >= mine: the clamped chunk again, into a buffer nobody reads)
-            const int64_t c0 = (slice + min(k, mine - 1) * nslices) * R;
+        auto commit = [&](int k, float4 (&pv)[8], float4 (&pm)[8]) {           // (k >= total: the last chunk again, into a buffer nobody reads)
+            const int64_t c0 = (int64_t)cc.c * R;
             if (M) {
     #pragma unroll
                 for (int j = 0; j < 8; ++j) {
@@ -476,9 +518,10 @@ wgrad3_kernel(const Wg2Args A) {
                 for (int j = 0; j < 8; ++j)
                     if (c0 + 8 * g + j >= N) pv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
             }
-            if (!is_x && k < mine) {
+            if (!is_x && k < total) {
     #pragma unroll
                 for (int j = 0; j < 8; ++j) { bs01 += bf3_f2{pv[j].x, pv[j].y}; bs23 += bf3_f2{pv[j].z, pv[j].w}; }
+                if (ends(cc)) bias_out(cc.s);                              // (scalar) the slice's last chunk
             }
             if (owner) {
                 __bf16* base = pl + (k & 1) * bufsz + (is_x ? 3 * O * P : 0) + 8 * g;
@@ -498,23 +541,26 @@ wgrad3_kernel(const Wg2Args A) {
                     *reinterpret_cast<uint4*>(col + 2 * cols * P + P) = make_uint4(bf3_pack(l[0].y, l[1].y), bf3_pack(l[2].y, l[3].y), bf3_pack(l[4].y, l[5].y), bf3_pack(l[6].y, l[7].y));
                 }
             }
+            step(cc);
         };
         __builtin_amdgcn_s_setprio(2);     // (the staging waves' vector work first: measured 3750 against 4100 cycles per chunk)
-        if (mine > 0) {
-            issue(0, pv0, pm0);
-            issue(1, pv1, pm1);
+        if (total > 0) {
+            issue(pv0, pm0);
+            issue(pv1, pm1);
             commit(0, pv0, pm0);
-            issue(2, pv0, pm0);
+            issue(pv0, pm0);
         }
         __syncthreads();
-        for (int64_t k = 0; k < mine; k += 2) {
+        for (int k = 0; k < total; k += 2) {
             commit(k + 1, pv1, pm1);
-            issue(k + 3, pv1, pm1);
+            issue(pv1, pm1);
             __syncthreads();
             commit(k + 2, pv0, pm0);
-            issue(k + 4, pv0, pm0);
+            issue(pv0, pm0);
             __syncthreads();
         }
+        if (!is_x)
+            for (int v = nfull; v < nv; ++v) bias_out(pb + v * G);                 // (slices without rows: zeros)
     };
     f32x16 acc[TI];
 #pragma unroll
@@ -528,7 +574,7 @@ wgrad3_kernel(const Wg2Args A) {
 #pragma unroll
     for (int t = 0; t < TI; ++t) boff[t] = 3 * O * P + min(t * 32 + c, I - 1) * P + 8 * kg;
     auto ld8 = [&](const __bf16* ptr) { return __builtin_bit_cast(bf3_x8, *reinterpret_cast<const uint4*>(ptr)); };
-    auto multiply = [&](int64_t k) {
+    auto multiply = [&](int k) {
         const __bf16* bf = pl + (k & 1) * bufsz;
 #pragma unroll
         for (int ks = 0; ks < R / 16; ++ks) {
@@ -556,38 +602,50 @@ wgrad3_kernel(const Wg2Args A) {
     if (tr) __syncthreads();
     // Chunk k of this block is staged into buffer k & 1 during step k - 1 and multiplied during step k; the requests for k + 2
     // leave when k's registers are free (two named register sets, loop unrolled by two).  The two roles run their OWN loops with
-    // the same number of barriers (1 + 2 ceil(mine / 2)): in one shared loop the accumulators stay live across the staging code and the
+    // the same number of barriers (1 + 2 ceil(total / 2)): in one shared loop the accumulators stay live across the staging code and the
     // staging registers across the matrix code (140 spills).
-    float* out = A.slab + (int64_t)slice * A.slab_row;
+    // A slice's sums go to its slab row when its last chunk has been multiplied - after the barrier, while the staging waves
+    // are already at the next chunk - and the accumulators start over.
+    auto dump = [&](int s) {
+        if (!strip) return;
+        float* out = q.slab + (int64_t)s * A.slab_row + q.out_off;
+        // (the bounds through an opaque copy: the 64 store predicates are loop invariants otherwise, hoisted out of the chunk
+        //  loop and kept in 128 scalar registers the kernel does not have)
+        int Od = O, Id = I;
+        asm volatile("" : "+s"(Od), "+s"(Id));
+#pragma unroll
+        for (int t = 0; t < TI; ++t) {
+            const int i = t * 32 + c;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int orow = wave * 32 + (v & 3) + 8 * (v >> 2) + 4 * kg;
+                if (orow < Od && i < Id) out[(int64_t)orow * A.ldw + i] = acc[t][v];
+                acc[t][v] = 0.f;
+            }
+        }
+    };
     if (producer) {
         if (MASK && !is_x) produce(std::true_type{});
         else produce(std::false_type{});
     } else {
+        Cur mc = first;
         __syncthreads();
-        for (int64_t k = 0; k < mine; k += 2) {
+        for (int k = 0; k < total; k += 2) {
             if (strip) multiply(k);
-
+            const bool end0 = ends(mc);
+            const int s0 = mc.s;
+            step(mc);
             __syncthreads();
-
-            if (strip && k + 1 < mine) multiply(k + 1);
-
+            if (end0) dump(s0);
+            const bool more = k + 1 < total;
+            if (strip && more) multiply(k + 1);
+            const bool end1 = more && ends(mc);
+            const int s1 = mc.s;
+            step(mc);
             __syncthreads();
+            if (end1) dump(s1);
         }
-        if (strip) {
-#pragma unroll
-            for (int t = 0; t < TI; ++t) {
-                const int i = t * 32 + c;
-                for (int v = 0; v < 16; ++v) {
-                    const int orow = wave * 32 + (v & 3) + 8 * (v >> 2) + 4 * kg;
-                    if (orow < O && i < I) out[q.out_off + (int64_t)orow * A.ldw + i] = acc[t][v];
-                }
-            }
-        }
-    }
-    if (q.bias_off >= 0) {                            // (uniform) the four row groups' column sums, in row-group order
-        if (owner && !is_x) *reinterpret_cast<float4*>(coef + g * O + 4 * cg) = make_float4(bs01.x, bs01.y, bs23.x, bs23.y);
-        __syncthreads();
-        if (tid < O) out[q.bias_off + tid] = (coef[tid] + coef[O + tid]) + (coef[2 * O + tid] + coef[3 * O + tid]);
+        for (int v = nfull; v < nv; ++v) dump(pb + v * G);                         // (slices without rows: zeros)
     }
 }
 
@@ -609,8 +667,9 @@ bool wgrad2_ok(const kpgnn_wgrad_desc* d, const float* x) {
            al(d->dy) && al(x) && (!d->dy_mask || al(d->dy_mask));
 }
 
-Wg2Prob wgrad2_prob(const kpgnn_wgrad_desc* d, const float* x, int64_t out_off, int64_t bias_off) {
+Wg2Prob wgrad2_prob(const kpgnn_wgrad_desc* d, const float* x, int64_t out_off, int64_t bias_off, float* slab) {
     Wg2Prob q;
+    q.slab = slab;
     q.dy = d->dy; q.x = x; q.mask = d->dy_mask; q.xm = d->x_mean; q.xi = d->x_invstd; q.xg = d->x_gamma; q.xb = d->x_beta;
     q.xrelu = d->x_relu; q.dys = d->dy_stride; q.xs = d->x_stride; q.out_off = out_off; q.bias_off = bias_off;
     return q;
@@ -624,12 +683,11 @@ int wgrad2_slices(int64_t N, int nprob, int blocks) {
     return (int)(s < 1 ? 1 : s);
 }
 
-// Launches the problems of A; *nslices = slab rows written (the caller's reduction covers exactly those).
-int wgrad2_launch(Wg2Args& A, int math, int* nslices, hipStream_t s) {
+// The bf16-split kernel on `per_prob` blocks per problem, which walk the problem's A.nslices slices.
+int wgrad3_launch(const Wg2Args& A, int per_prob, hipStream_t s) {
     const int ti = (A.I + 31) / 32;
-    if (math != KPGNN_MATH_F32 && wgrad3_ok(A)) {
-        *nslices = wgrad2_slices(A.N, A.nprob, kW3Blocks);
-        dim3 gr3((unsigned)(*nslices * A.nprob)), blk3(512);
+    {
+        dim3 gr3((unsigned)(per_prob * A.nprob)), blk3(512);
         const size_t lds3 = wgrad3_lds(A);
         const bool mask = A.q[0].mask != nullptr;      // (the problems of a launch share dy and its mask, or have none)
 #define KP_W3(T) do { if (mask) { KPGNN_HIP_TRY(ensure_dynamic_lds((const void*)wgrad3_kernel<T, true>, lds3)); \
@@ -646,7 +704,16 @@ int wgrad2_launch(Wg2Args& A, int math, int* nslices, hipStream_t s) {
         KPGNN_LAUNCH_CHECK("wgrad3_kernel");
         return KPGNN_OK;
     }
-    *nslices = wgrad2_slices(A.N, A.nprob, kWgradBlocks);
+}
+
+// Launches the problems of A; *nslices = slab rows written (the caller's reduction covers exactly those).
+int wgrad2_launch(Wg2Args& A, int math, int* nslices, hipStream_t s) {
+    const int ti = (A.I + 31) / 32;
+    if (math != KPGNN_MATH_F32 && wgrad3_ok(A)) {
+        *nslices = A.nslices = wgrad2_slices(A.N, A.nprob, kW3Blocks);
+        return wgrad3_launch(A, *nslices, s);                 // a block per slice
+    }
+    *nslices = A.nslices = wgrad2_slices(A.N, A.nprob, kWgradBlocks);
     dim3 gr((unsigned)(*nslices * A.nprob)), blk(256);
     const size_t lds = sizeof(float) * ((size_t)kW2Rows * (A.O + A.I) + 4 * (size_t)A.I);
 #define KP_W2(T) hipLaunchKernelGGL((wgrad2_kernel<T>), gr, blk, lds, s, A)
@@ -685,8 +752,8 @@ extern "C" int kpgnn_linear_wgrad(const kpgnn_wgrad_desc* d, kpgnn_stream_t stre
     int grid;
     if (wgrad2_ok(d, d->x)) {
         Wg2Args A;
-        A.N = d->N; A.n_dyn = d->n_dyn; A.O = d->O; A.I = d->I; A.nprob = 1; A.ldw = d->I; A.slab = slab; A.slab_row = nw + d->O;
-        for (int i = 0; i < kW2MaxProb; ++i) A.q[i] = wgrad2_prob(d, d->x, 0, nw);
+        A.N = d->N; A.n_dyn = d->n_dyn; A.O = d->O; A.I = d->I; A.nprob = 1; A.ldw = d->I; A.slab_row = nw + d->O;
+        for (int i = 0; i < kW2MaxProb; ++i) A.q[i] = wgrad2_prob(d, d->x, 0, nw, slab);
         rc = wgrad2_launch(A, d->math, &grid, s);
     } else {
         KPGNN_REQUIRE(!d->dy_mask && !d->n_dyn, "linear_wgrad: dy_mask / n_dyn need 16-B aligned operands with O %% 4 == I %% 4 == 0, O <= 128");
@@ -721,9 +788,9 @@ extern "C" int kpgnn_linear_wgrad_pair(const kpgnn_wgrad_desc* a, const kpgnn_wg
     int grid;
     if (wgrad2_ok(a, a->x) && wgrad2_ok(b, b->x)) {
         Wg2Args A;
-        A.N = a->N; A.n_dyn = a->n_dyn; A.O = a->O; A.I = a->I; A.nprob = 2; A.ldw = a->I; A.slab = slab; A.slab_row = 2 * one;
-        for (int i = 0; i < kW2MaxProb; ++i) A.q[i] = wgrad2_prob(a, a->x, 0, nw);
-        A.q[1] = wgrad2_prob(b, b->x, one, one + nw);
+        A.N = a->N; A.n_dyn = a->n_dyn; A.O = a->O; A.I = a->I; A.nprob = 2; A.ldw = a->I; A.slab_row = 2 * one;
+        for (int i = 0; i < kW2MaxProb; ++i) A.q[i] = wgrad2_prob(a, a->x, 0, nw, slab);
+        A.q[1] = wgrad2_prob(b, b->x, one, one + nw, slab);
         rc = wgrad2_launch(A, a->math, &grid, s);
     } else {
         KPGNN_REQUIRE(!a->dy_mask && !b->dy_mask && !a->n_dyn, "linear_wgrad_pair: dy_mask / n_dyn need 16-B aligned operands");
@@ -742,6 +809,62 @@ extern "C" int kpgnn_linear_wgrad_pair(const kpgnn_wgrad_desc* a, const kpgnn_wg
         return KPGNN_OK;
     }
     return slab_reduce(slab, grid, 2 * one, a->dw, nw, a->db, a->O, b->dw, s, nw, b->db);
+}
+
+extern "C" int kpgnn_linear_wgrad_many(const kpgnn_wgrad_desc* const* a, const kpgnn_wgrad_desc* const* b, int32_t count,
+                                       kpgnn_stream_t stream) {
+    KPGNN_REQUIRE(a != nullptr && b != nullptr && count >= 1 && 2 * count <= kW2MaxProb,
+                  "linear_wgrad_many: bad arguments (1 <= count <= %d)", kW2MaxProb / 2);
+    for (int p = 0; p < count; ++p) KPGNN_REQUIRE(a[p] && b[p], "linear_wgrad_many: pair %d is missing", p);
+    // One launch serves pairs of one shape on the bf16-split kernel; everything else is the pair entry's, pair by pair.
+    bool one = count > 1 && a[0]->math != KPGNN_MATH_F32;
+    for (int p = 0; p < count && one; ++p) {
+        const kpgnn_wgrad_desc *x = a[p], *y = b[p];
+        one = wgrad_check(x, "linear_wgrad_many") == KPGNN_OK && wgrad_check(y, "linear_wgrad_many") == KPGNN_OK &&
+              x->N == a[0]->N && y->N == a[0]->N && x->O == a[0]->O && y->O == a[0]->O && x->I == a[0]->I && y->I == a[0]->I &&
+              x->n_dyn == a[0]->n_dyn && y->n_dyn == a[0]->n_dyn && x->math == a[0]->math && x->db && y->db &&
+              x->workspace && x->workspace_bytes >= 2 * kpgnn_wgrad_workspace_bytes(x->O, x->I) &&
+              wgrad2_ok(x, x->x) && wgrad2_ok(y, y->x);
+    }
+    Wg2Args A;
+    int64_t nw = 0, row = 0;
+    if (one) {
+        nw = (int64_t)a[0]->O * a[0]->I; row = nw + a[0]->O;
+        A.N = a[0]->N; A.n_dyn = a[0]->n_dyn; A.O = a[0]->O; A.I = a[0]->I; A.nprob = 2 * count; A.ldw = a[0]->I; A.slab_row = 2 * row;
+        for (int i = 0; i < kW2MaxProb; ++i) {
+            const int p = i < 2 * count ? i / 2 : 0;
+            float* slab = (float*)a[p]->workspace;
+            A.q[i] = i % 2 == 0 ? wgrad2_prob(a[p], a[p]->x, 0, nw, slab) : wgrad2_prob(b[p], b[p]->x, row, row + nw, slab);
+        }
+        one = wgrad3_ok(A);
+    }
+    if (!one) {
+        for (int p = 0; p < count; ++p) {
+            const int rc = kpgnn_linear_wgrad_pair(a[p], b[p], stream);
+            if (rc != KPGNN_OK) return rc;
+        }
+        return KPGNN_OK;
+    }
+    // Every pair keeps the slicing of its own launch - the slab rows, and so the sums, are the pair entry's bit for bit - but
+    // the chip's blocks are shared out among all the problems: each walks several slices of one problem.
+    hipStream_t s = (hipStream_t)stream;
+    A.nslices = wgrad2_slices(A.N, 2, kW3Blocks);
+    const int per_prob = A.nslices < kW3Blocks / A.nprob ? A.nslices : kW3Blocks / A.nprob;
+    int rc = wgrad3_launch(A, per_prob, s);
+    if (rc != KPGNN_OK) return rc;
+    for (int p = 0; p < count; ++p) {
+        float* slab = (float*)a[p]->workspace;
+        if (a[p]->defer) {
+            kpgnn_reduce_job* j = a[p]->defer;
+            j->slab = slab; j->nslab = A.nslices; j->elems = 2 * row;
+            j->out[0] = a[p]->dw; j->n_out[0] = nw; j->out[1] = a[p]->db; j->n_out[1] = A.O;
+            j->out[2] = b[p]->dw; j->n_out[2] = nw; j->out[3] = b[p]->db; j->n_out[3] = A.O;
+            continue;
+        }
+        rc = slab_reduce(slab, A.nslices, 2 * row, a[p]->dw, nw, a[p]->db, A.O, b[p]->dw, s, nw, b[p]->db);
+        if (rc != KPGNN_OK) return rc;
+    }
+    return KPGNN_OK;
 }
 
 extern "C" size_t kpgnn_wgrad_group_workspace_bytes(int32_t O, int32_t I, int32_t group) {
@@ -763,19 +886,20 @@ extern "C" int kpgnn_linear_wgrad_group(const kpgnn_wgrad_desc* d, const float* 
     const int64_t nw = (int64_t)d->O * d->I * group;
     Wg2Args A;
     A.N = d->N; A.n_dyn = d->n_dyn; A.O = d->O; A.I = d->I; A.nprob = group; A.ldw = (int64_t)d->I * group;
-    A.slab = (float*)d->workspace; A.slab_row = nw + d->O;
-    for (int i = 0; i < kW2MaxProb; ++i) A.q[i] = wgrad2_prob(d, x_group[i < group ? i : 0], (int64_t)(i < group ? i : 0) * d->I, i == 0 ? nw : -1);
+    float* slab = (float*)d->workspace;
+    A.slab_row = nw + d->O;
+    for (int i = 0; i < kW2MaxProb; ++i) A.q[i] = wgrad2_prob(d, x_group[i < group ? i : 0], (int64_t)(i < group ? i : 0) * d->I, i == 0 ? nw : -1, slab);
     int grid = 0;
     hipStream_t s = (hipStream_t)stream;
     rc = wgrad2_launch(A, d->math, &grid, s);
     if (rc != KPGNN_OK) return rc;
-    float* db = d->db ? d->db : A.slab + (size_t)grid * A.slab_row;     // sink behind the slab rows
+    float* db = d->db ? d->db : slab + (size_t)grid * A.slab_row;     // sink behind the slab rows
     if (d->defer) {
         kpgnn_reduce_job* j = d->defer;
-        j->slab = A.slab; j->nslab = grid; j->elems = nw + d->O;
+        j->slab = slab; j->nslab = grid; j->elems = nw + d->O;
         j->out[0] = d->dw; j->n_out[0] = nw; j->out[1] = db; j->n_out[1] = d->O;
         j->out[2] = j->out[3] = nullptr; j->n_out[2] = j->n_out[3] = 0;
         return KPGNN_OK;
     }
-    return slab_reduce(A.slab, grid, nw + d->O, d->dw, nw, db, d->O, nullptr, s);
+    return slab_reduce(slab, grid, nw + d->O, d->dw, nw, db, d->O, nullptr, s);
 }

@@ -122,7 +122,14 @@ def _check_codes(csr, k_act, table0, tablek):
 # is left when the block ends is run then.  The gradient tensors such a backward returns are NOT valid until the block
 # ends: only for callers that read gradients afterwards (torch.autograd.grad(...) inside the block, or .backward() into
 # parameters whose .grad is None) - never with gradient accumulation into existing .grad tensors or backward hooks.
+#
+# The weight gradients of the fused MLPs go one step further: nothing reads them before the pass ends, so inside the block
+# their PRODUCTS are not launched either.  Each MLP parks its pair of problems here, and up to WGRAD_MANY_PAIRS of one shape
+# run as ONE kpgnn_linear_wgrad_many launch (per pair the sums of a launch of its own, bit for bit) followed by their
+# reductions.  A parked pair keeps its operands alive until then (dy2, dy1, y1, h: 4 [N,h] tensors per layer).
 _pending_reduce = None        # None: off; list of (ReduceJob, tensors kept alive)
+_parked_wgrad = []            # (shape key, WgradDesc a, WgradDesc b, parameter keys, tensors kept alive), oldest first
+WGRAD_MANY_PAIRS = 8          # csrc/wgrad.hip kW2MaxProb / 2
 
 
 class deferred_reductions:
@@ -136,6 +143,9 @@ class deferred_reductions:
     def __exit__(self, *exc):
         global _pending_reduce
         if self._outer is None:
+            if exc[0] is None:
+                flush_parked_wgrad()
+            del _parked_wgrad[:]
             jobs, _pending_reduce = _pending_reduce, None
             _deferred_owners.clear()
             if jobs and exc[0] is None:
@@ -162,6 +172,7 @@ def defer_reduce_job(*params):
         return None
     keys = {p.data_ptr() for p in params if p is not None}
     if keys & _deferred_owners:
+        flush_parked_wgrad()          # (the parked products first: their reductions must not run after the sum either)
         jobs = list(_pending_reduce)
         del _pending_reduce[:]
         _deferred_owners.clear()
@@ -170,6 +181,47 @@ def defer_reduce_job(*params):
         return None
     _deferred_owners.update(keys)
     return _lib.ReduceJob()
+
+
+def park_wgrad_pair(a, b, params, keep_alive):
+    """Inside deferred_reductions(): take the two weight-gradient problems of a fused MLP (filled kpgnn_wgrad_desc a, b with
+    O == I, a.workspace set) instead of launching them - True - where the bf16-split kernel would run them.  False: the caller
+    launches as usual.  `params` as in defer_reduce_job; keep_alive[0] is a tensor on the launch's device."""
+    if _pending_reduce is None or a.math == _lib.MATH_F32 or a.O != a.I or a.O > 128 or a.O % 4:
+        return False
+    keys = {p.data_ptr() for p in params}
+    if keys & _deferred_owners:       # a shared weight: defer_reduce_job runs what is parked and queued, the caller reduces at once
+        return False
+    shape = (a.N, a.O, a.I, a.n_dyn, keep_alive[0].device)
+    if _parked_wgrad and _parked_wgrad[0][0] != shape:
+        flush_parked_wgrad()
+    _deferred_owners.update(keys)
+    _parked_wgrad.append((shape, a, b, keys, keep_alive))
+    if len(_parked_wgrad) == WGRAD_MANY_PAIRS:
+        flush_parked_wgrad()
+    return True
+
+
+def flush_parked_wgrad():
+    """Run the parked weight-gradient products in one launch, then their reductions."""
+    parked = list(_parked_wgrad)
+    del _parked_wgrad[:]
+    if not parked:
+        return
+    dev = parked[0][0][-1]
+    jobs = []
+    for _, a, _, keys, keep_alive in parked:
+        job = _lib.ReduceJob()
+        a.defer = ctypes.cast(ctypes.pointer(job), ctypes.c_void_p)
+        jobs.append((job, keep_alive))
+        _deferred_owners.difference_update(keys)
+    if len(parked) == 1:
+        _lib.launch("kpgnn_linear_wgrad_pair", dev, ctypes.byref(parked[0][1]), ctypes.byref(parked[0][2]))
+    else:
+        ptrs = ctypes.POINTER(_lib.WgradDesc) * len(parked)
+        _lib.launch("kpgnn_linear_wgrad_many", dev, ptrs(*[ctypes.pointer(e[1]) for e in parked]),
+                    ptrs(*[ctypes.pointer(e[2]) for e in parked]), len(parked))
+    flush_reductions(jobs)
 
 
 def queue_reduce_job(job, keep_alive):

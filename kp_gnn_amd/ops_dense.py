@@ -527,12 +527,14 @@ class FusedMLP(torch.autograd.Function):
             nb = 2 * int(lib.kpgnn_wgrad_workspace_bytes(O, O))
             ws = torch.empty(nb, dtype=torch.uint8, device=dev)
             a.workspace, a.workspace_bytes = ws.data_ptr(), nb
-            job = ops.defer_reduce_job(w0, w3)    # (inside ops.deferred_reductions(): the reduce rides with a later launch)
-            if job is not None:
-                a.defer = ctypes.cast(ctypes.pointer(job), ctypes.c_void_p)
-            _lib.launch("kpgnn_linear_wgrad_pair", dev, ctypes.byref(a), ctypes.byref(b))
-            if job is not None:
-                ops.queue_reduce_job(job, (ws, dw3, dw0, db))
+            # inside ops.deferred_reductions(): the pair waits for the pass's one weight-gradient launch (with its operands) ...
+            if not ops.park_wgrad_pair(a, b, (w0, w3), (ws, dw3, dw0, db, dy2, dy1, y1, h, st, g1, be1)):
+                job = ops.defer_reduce_job(w0, w3)    # ... or at least its reduce rides with a later launch
+                if job is not None:
+                    a.defer = ctypes.cast(ctypes.pointer(job), ctypes.c_void_p)
+                _lib.launch("kpgnn_linear_wgrad_pair", dev, ctypes.byref(a), ctypes.byref(b))
+                if job is not None:
+                    ops.queue_reduce_job(job, (ws, dw3, dw0, db))
         else:
             for q in (a, b):
                 nb = int(lib.kpgnn_wgrad_workspace_bytes(q.O, q.I))
