@@ -1721,6 +1721,26 @@ typedef struct kpgnn_graph_labels_desc {
 int kpgnn_graph_labels(const kpgnn_graph_labels_desc* d, kpgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The same six labels for graphs of up to KPGNN_GL_LARGE_MAX_NODES nodes (csrc/graph_labels_large.hip): the third size class.
+ * The descriptor, the labels, the six status codes with their precedence and the output contract are kpgnn_graph_labels's:
+ * status is written for every graph of `graph_ids`, node_out / graph_out only where it is 0, n == 0 writes status 0 and a zero
+ * graph_out row, n > max_nodes of the launch is KPGNN_GL_TOO_LARGE.  One 256-thread block per graph, whatever max_nodes; a row
+ * is TWO 64-bit words in LDS (bit 64 is bit 0 of the second), the n x n double matrix of the spectral radius lives in LDS too
+ * (128 x 129 doubles next to 11.5 KB of rows and vectors: one block per CU at max_nodes = 128, the launch's dynamic LDS is
+ * sized by max_nodes).  Any n from 1 to the cap is served; the caller sends the graphs of 65 nodes and more.
+ * is_connected is m = 1 + ceil(log2 n) BOOLEAN squarings here too.  For 65 <= n <= 128, m = 8 and every entry of A^(2^7) is at
+ * most 127^128 < 2^895, so the reference's last float64 squaring multiplies no inf by 0: it makes no nan and rounds no positive
+ * integer to zero.  Hence its min > 0 holds iff the eighth boolean squaring has no zero - exactly, dense graphs included (K128
+ * overflows to inf, which is > 0); at n = 129, m = 9 and stage 8 can hold inf next to zeros, which is why the cap is 128.
+ * No global atomics, no float atomics, every cross-lane sum in index order: the bits of a graph depend on that graph alone.
+ * G == 0 or n_ids == 0 return KPGNN_OK without a launch.  max_nodes < 1 is KPGNN_EINVAL and > 128 KPGNN_ELIMIT, before any
+ * device call.
+ * ---------------------------------------------------------------------------------------------- */
+#define KPGNN_GL_LARGE_MAX_NODES 128
+
+int kpgnn_graph_labels_large(const kpgnn_graph_labels_desc* d, kpgnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Labels of the synthetic substructure-counting dataset (csrc/count_labels.hip; datasets/GraphCountDataset.py process).  For
  * each graph g of n = node_ptr[g+1] - node_ptr[g] nodes, with A the symmetric 0/1 adjacency of its edges (duplicates
  * collapse), d_i the degree of node i, c_ij = popcount(row_i & row_j) = (A^2)_ij and T_i = sum_{j in N(i)} c_ij = (A^3)_ii:

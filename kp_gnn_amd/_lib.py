@@ -443,6 +443,7 @@ COLLISION_MAX_D = 256                                                   # csrc/c
 
 GL_OK, GL_ASYMMETRIC, GL_TOO_LARGE, GL_ENDPOINT, GL_SELF_LOOP, GL_SOURCE = 0, 1, 2, 3, 4, 5    # include/kpgnn.h KPGNN_GL_*
 GL_MAX_NODES, GL_WAVE_NODES = 64, 32                                    # KPGNN_GL_MAX_NODES, KPGNN_GL_WAVE_NODES
+GL_LARGE_MAX_NODES = 128                                                # KPGNN_GL_LARGE_MAX_NODES (kpgnn_graph_labels_large)
 
 
 class GraphLabelsDesc(ctypes.Structure):
@@ -586,6 +587,7 @@ SIGNATURES = {
     "kpgnn_collision_workspace_bytes": (c_i64, [c_i64]),
     "kpgnn_collision_count": (ctypes.c_int, [ctypes.POINTER(CollisionDesc), c_vp]),
     "kpgnn_graph_labels": (ctypes.c_int, [ctypes.POINTER(GraphLabelsDesc), c_vp]),
+    "kpgnn_graph_labels_large": (ctypes.c_int, [ctypes.POINTER(GraphLabelsDesc), c_vp]),
     "kpgnn_count_labels_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "kpgnn_count_labels": (ctypes.c_int, [ctypes.POINTER(CountLabelsDesc), c_vp]),
     "kpgnn_vn_add_pool": (ctypes.c_int, [ctypes.POINTER(VnDesc), c_vp]),

@@ -144,22 +144,29 @@ def resistance_distance(node_ptr, edge_ptr, edge_index, device, large="host", wo
 GRAPH_LABELS_AUTO = "device"     # graph_property_labels(route="auto"): DESIGN.md 5.24 has the measurement behind it
 
 
-def graph_labels_plan(nodes):
-    """The launches of graph_property_labels: the wavefront class, then the block class with every larger graph (status 2)."""
-    return size_classes("kpgnn_graph_labels", nodes, (_lib.GL_WAVE_NODES, _lib.GL_MAX_NODES), largest_member(_lib.GL_MAX_NODES))
+def graph_labels_plan(nodes, large="host"):
+    """The launches of graph_property_labels: the wavefront class, then the block class with every graph no class serves
+    (status 2) and, for large="device", the graphs of 65 .. GL_LARGE_MAX_NODES nodes as one kpgnn_graph_labels_large launch
+    sized for its largest member."""
+    big = (nodes > _lib.GL_MAX_NODES) & (nodes <= _lib.GL_LARGE_MAX_NODES) & (large == "device")
+    plan = size_classes("kpgnn_graph_labels", nodes, (_lib.GL_WAVE_NODES, _lib.GL_MAX_NODES), largest_member(_lib.GL_MAX_NODES), big)
+    if big.any():
+        plan.append(("kpgnn_graph_labels_large", np.flatnonzero(big), int(nodes[big].max()), 0))
+    return plan
 
 
-def graph_labels_launch(G, nptr, eptr, ei, E, feat, src, ids, max_nodes, node_out, graph_out, status):
-    """One kpgnn_graph_labels launch over device tensors: the graphs `ids` (int32) of a call of G graphs, sized for max_nodes."""
+def graph_labels_launch(G, nptr, eptr, ei, E, feat, src, ids, max_nodes, node_out, graph_out, status, entry="kpgnn_graph_labels"):
+    """One launch of `entry` (kpgnn_graph_labels or kpgnn_graph_labels_large: one descriptor) over device tensors: the graphs
+    `ids` (int32) of a call of G graphs, sized for max_nodes."""
     d = _lib.GraphLabelsDesc()
     d.G, d.n_ids, d.E, d.max_nodes = G, ids.numel(), E, max_nodes
     d.node_ptr, d.edge_ptr, d.edge_index, d.graph_ids = nptr.data_ptr(), eptr.data_ptr(), ei.data_ptr(), ids.data_ptr()
     d.features, d.source = feat.data_ptr(), src.data_ptr()
     d.node_out, d.graph_out, d.status = node_out.data_ptr(), graph_out.data_ptr(), status.data_ptr()
-    _lib.launch("kpgnn_graph_labels", node_out.device, ctypes.byref(d))
+    _lib.launch(entry, node_out.device, ctypes.byref(d))
 
 
-def graph_property_labels(node_ptr, edge_ptr, edge_index, features, source, device, route="auto"):
+def graph_property_labels(node_ptr, edge_ptr, edge_index, features, source, device, route="auto", large="host"):
     """The labels of the reference's graph- and node-property dataset (datasets/GraphPropertyDataset.py genereate_dataset) of G
     raw graphs at once: (node_labels [N,3] float32: sssp | eccentricity | laplacian features, graph_labels [G,3] float32:
     is_connected | diameter | spectral_radius), both on `device`.  node_ptr / edge_ptr [G+1]: host offsets; edge_index [2,E]
@@ -171,9 +178,15 @@ def graph_property_labels(node_ptr, edge_ptr, edge_index, features, source, devi
     endpoint outside its graph (3), a self loop (4) and a source outside its graph (5) raise ValueError naming the first such
     graph.  route "host": graph_property.graph_property_labels_host, moved to the device.  "auto" is GRAPH_LABELS_AUTO.  The
     integer labels are the same whichever route served a graph; the two float64 computations of the spectral radius and of
-    the laplacian column may differ in the last float32 bit."""
+    the laplacian column may differ in the last float32 bit.
+    large (route "device" only): who serves a graph of 65 to 128 nodes.  "host", the default: nobody on the device - it gets
+    status 2 from the block-class launch and labels_host_f64 fills it.  "device": a third class, 64 < n <= GL_LARGE_MAX_NODES,
+    goes to kpgnn_graph_labels_large (csrc/graph_labels_large.hip: two words per row, the double matrix in LDS, a block per
+    graph) in one more launch sized for its largest member; status 2 is then n > 128, and the status is still read once."""
     if route not in ("auto", "device", "host"):
         raise ValueError(f"unknown route {route!r}")
+    if large not in ("host", "device"):
+        raise ValueError(f"unknown large {large!r}: 'host' or 'device'")
     route = GRAPH_LABELS_AUTO if route == "auto" else route
     dev = torch.device(device)
     if route == "host":
@@ -194,11 +207,11 @@ def graph_property_labels(node_ptr, edge_ptr, edge_index, features, source, devi
     src = torch.from_numpy(np.clip(g.source, -1, 1 << 30).astype(np.int32)).to(dev)     # (any value outside [0, n) is status 5)
     st = torch.empty(g.G, dtype=torch.int32, device=dev)
     launch = lambda entry, ids, max_nodes, ws, nbytes: graph_labels_launch(  # noqa: E731
-        g.G, nptr, eptr, ei, g.E, feat, src, ids, max_nodes, node_out, graph_out, st)
+        g.G, nptr, eptr, ei, g.E, feat, src, ids, max_nodes, node_out, graph_out, st, entry=entry)
     what = {_lib.GL_ENDPOINT: lambda i: f"an edge endpoint lies outside its nodes [0, {int(g.nodes[i])})",
             _lib.GL_SELF_LOOP: lambda i: "a self loop (the labels are defined for graphs without one)",
             _lib.GL_SOURCE: lambda i: f"source {int(g.source[i])} lies outside its nodes [0, {int(g.nodes[i])})"}
-    _, todo = run_plan(graph_labels_plan(g.nodes), dev, launch, st, [(tuple(what), lambda i, code: ValueError(f"graph {i}: {what[code](i)}"))])
+    _, todo = run_plan(graph_labels_plan(g.nodes, large), dev, launch, st, [(tuple(what), lambda i, code: ValueError(f"graph {i}: {what[code](i)}"))])
     if todo.size:
         node_h, graph_h = GP.labels_host_f64(g.node_ptr, g.edge_ptr, g.edge_index, features, g.source, graphs=todo)
         rows = torch.from_numpy(np.concatenate([np.arange(g.node_ptr[i], g.node_ptr[i + 1]) for i in todo])).to(dev)
