@@ -1721,7 +1721,7 @@ typedef struct kpgnn_graph_labels_desc {
 int kpgnn_graph_labels(const kpgnn_graph_labels_desc* d, kpgnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * The same six labels for graphs of up to KPGNN_GL_LARGE_MAX_NODES nodes (csrc/graph_labels_large.hip): the third size class.
+ * The same six labels for graphs of up to KPGNN_GL_LARGE_MAX_NODES nodes (csrc/graph_labels.hip, W = 2): the third size class.
  * The descriptor, the labels, the six status codes with their precedence and the output contract are kpgnn_graph_labels's:
  * status is written for every graph of `graph_ids`, node_out / graph_out only where it is 0, n == 0 writes status 0 and a zero
  * graph_out row, n > max_nodes of the launch is KPGNN_GL_TOO_LARGE.  One 256-thread block per graph, whatever max_nodes; a row

@@ -113,17 +113,6 @@ __device__ __forceinline__ int status_of(const int* flags) {
     return flags[0] ? KPGNN_CL_ENDPOINT : flags[1] ? KPGNN_CL_SELF_LOOP : flags[2] ? KPGNN_CL_ASYMMETRIC : KPGNN_CL_OK;
 }
 
-template <bool WAVE>
-__device__ __forceinline__ void team_sync() {
-    if (WAVE) {     // one wavefront: LDS operations of a wave complete in order; keep the compiler from moving them
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    } else {
-        __syncthreads();
-    }
-}
-
 // ---------------------------------------------------------------------------------------------- n <= 64: one-word rows in LDS
 template <int CAP, int NQ>
 struct WordTeam {

@@ -54,17 +54,6 @@ __host__ __device__ constexpr size_t team_bytes(int cap, int K, int threads) {
     return ((2 * mat_words(cap) * 4 + w_bytes(cap, threads) + 7) & ~(size_t)7) + (size_t)cap * K * 8 + (size_t)cap * 8 + 16;
 }
 
-template <bool WAVE>
-__device__ __forceinline__ void team_sync() {
-    if (WAVE) {     // one wavefront: LDS operations of a wave complete in order; keep the compiler from moving them
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    } else {
-        __syncthreads();
-    }
-}
-
 __device__ __forceinline__ uint64_t below(int j) { return ((uint64_t)1 << j) - 1; }     // j in [0, 63]
 
 // Peripheral statistics of the subgraph induced on S, the hop word of (node, hop): peripheral_stats of khop_host.cpp.

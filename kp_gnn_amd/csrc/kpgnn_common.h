@@ -54,6 +54,18 @@ __device__ __forceinline__ T live_rows(T N, const int32_t* n_dyn) {
 }
 constexpr int kNumXcd = 8;  // MI355X: 8 XCDs, blocks are dealt round-robin over them
 
+// The barrier of a team that owns one graph in LDS (the raw-graph dataset kernels): a wavefront (WAVE) or a whole block.
+template <bool WAVE>
+__device__ __forceinline__ void team_sync() {
+    if (WAVE) {     // one wavefront: LDS operations of a wave complete in order; keep the compiler from moving them
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    } else {
+        __syncthreads();
+    }
+}
+
 // Sum over the L lanes of a sub-group (L a power of two <= 64, the sub-group aligned to L lanes): a butterfly with the offsets
 // L/2, L/4, ..., 1, so every lane ends with the same bits and the sum never leaves the sub-group's wave.
 template <int L> __device__ __forceinline__ float group_sum(float v) {

@@ -41,17 +41,6 @@ __host__ __device__ constexpr size_t team_bytes(int cap) {
 }
 
 template <bool WAVE>
-__device__ __forceinline__ void team_sync() {
-    if (WAVE) {     // one wavefront: LDS operations of a wave complete in order; keep the compiler from moving them
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    } else {
-        __syncthreads();
-    }
-}
-
-template <bool WAVE>
 __global__ void __launch_bounds__(kBlock) rd_kernel(const RdParams p) {
     extern __shared__ double rd_lds[];
     constexpr int T = WAVE ? kWave : kBlock;

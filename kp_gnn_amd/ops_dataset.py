@@ -181,7 +181,7 @@ def graph_property_labels(node_ptr, edge_ptr, edge_index, features, source, devi
     the laplacian column may differ in the last float32 bit.
     large (route "device" only): who serves a graph of 65 to 128 nodes.  "host", the default: nobody on the device - it gets
     status 2 from the block-class launch and labels_host_f64 fills it.  "device": a third class, 64 < n <= GL_LARGE_MAX_NODES,
-    goes to kpgnn_graph_labels_large (csrc/graph_labels_large.hip: two words per row, the double matrix in LDS, a block per
+    goes to kpgnn_graph_labels_large (csrc/graph_labels.hip, W = 2: two words per row, the double matrix in LDS, a block per
     graph) in one more launch sized for its largest member; status 2 is then n > 128, and the status is still read once."""
     if route not in ("auto", "device", "host"):
         raise ValueError(f"unknown route {route!r}")

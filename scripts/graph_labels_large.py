@@ -1,5 +1,5 @@
 """ops.graph_property_labels on graphs of 65 to 100 nodes - the reference's extrapolation sizes: large="device", the kernel of
-csrc/graph_labels_large.hip, against large="host", the default, which leaves every such graph to the float64 numpy route.
+csrc/graph_labels.hip (W = 2), against large="host", the default, which leaves every such graph to the float64 numpy route.
 
     python scripts/graph_labels_large.py --out profiles/graph_labels_large/graph_labels_large.json
     python scripts/graph_labels_large.py --graphs 200 --rounds 1                # a smaller look

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the graph-property label kernel of graphs of up to 128 nodes (csrc/graph_labels_large.hip), through
+"""GPU (-m gpu): the graph-property label kernel of graphs of up to 128 nodes (csrc/graph_labels.hip, W = 2), through
 ops.graph_property_labels(large="device") and through raw kpgnn_graph_labels_large launches into poisoned outputs.
 
 The rules are those of test_graph_property.py (check_case): the four integer labels bit-exact as float32, the spectral radius

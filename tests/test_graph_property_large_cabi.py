@@ -1,5 +1,5 @@
 """CPU: the C ABI of the graph-property labels' third size class (include/kpgnn.h kpgnn_graph_labels_large,
-csrc/graph_labels_large.hip) - declaration, export, binding, the argument checks that run before any device call - and the
+csrc/graph_labels.hip, W = 2) - declaration, export, binding, the argument checks that run before any device call - and the
 launch plan of ops.graph_property_labels(large=)."""
 import ctypes
 import os

@@ -1,4 +1,4 @@
-"""CPU: what lets the device serve the graph-property labels of graphs of 65 to 128 nodes (csrc/graph_labels_large.hip).
+"""CPU: what lets the device serve the graph-property labels of graphs of 65 to 128 nodes (csrc/graph_labels.hip, W = 2).
 1. The overflow argument as a test: for 65 <= n <= 128 the reference squares m = 8 times, no entry is inf when the last
    squaring begins, so it forms no inf * 0 and its min > 0 is "the eighth boolean squaring has no zero" - on 145 graphs,
    dense ones included (K128 overflows to inf, which is > 0).
