@@ -1798,6 +1798,51 @@ typedef struct kpgnn_count_labels_desc {
 size_t kpgnn_count_labels_workspace_bytes(int max_nodes);
 int kpgnn_count_labels(const kpgnn_count_labels_desc* d, kpgnn_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Uniform random simple d-regular graphs: the pairing model with rejection (csrc/regular_graphs.hip; the same bits from
+ * kp_gnn_amd/regular_graphs.py on the host).  The definition, which no launch geometry enters: graph g of a call is a
+ * function of (seed, first_graph + g, n, d) alone.
+ *   stubs     m = n * d of them; stub s belongs to node s / d.
+ *   words     pairing number a = 0, 1, .. draws one 64-bit word r(s) per stub: with (w0, w1, w2, w3) the output of
+ *             Philox4x32-10 (ten rounds, multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85 - the
+ *             function behind kpgnn_dropout_*) under the key (seed & 0xFFFFFFFF, seed >> 32) at the counter
+ *             (s >> 1, a, id & 0xFFFFFFFF, id >> 32), id = (uint64_t)(first_graph + g):
+ *             r(s) = w[2 (s & 1)] | w[2 (s & 1) + 1] << 32.
+ *   key       (r(s) & ~0x1FFF) | s: 51 random bits above the 13-bit stub index, so no two keys are equal and the order is
+ *             total whatever sorts them.
+ *   pairing   sort the m keys ascending; the stubs at the sorted positions 2 i and 2 i + 1 are partners.
+ *   accepted  when no stub's partner lies in the stub's own node (no self loop) and no node has two stubs whose partners lie
+ *             in one node (no double edge).  Every simple d-regular graph on n labelled nodes then comes out with the same
+ *             probability.  Otherwise a increases by one; after max_attempts pairings the graph is EXHAUSTED.
+ *   output    node u's d neighbours ascending, as the directed edges (u, v) at the columns g * m + u * d + j of
+ *             edge_index [2, G * m] (LOCAL ids): the (src, dst)-sorted list of batch.regular_graphs, with
+ *             node_ptr[g] = g * n and edge_ptr[g] = g * m.  attempts[g] = the pairings drawn (max_attempts when exhausted).
+ * status[g]: KPGNN_RRG_OK 0, or KPGNN_RRG_EXHAUSTED 1 - the columns of such a graph are NOT written.
+ * One team per graph for its whole rejection loop: the keys, padded with all-ones keys to the next power of two P >= m, are
+ * sorted by a bitonic network in LDS (8 P bytes, and 2 m for the partner table: 80 KiB at the limit), the two checks end in a
+ * team-wide vote, and the accepted rows are written by one thread per node.  m <= KPGNN_RRG_WAVE_STUBS: a wavefront per
+ * graph, four graphs per 256-thread block, no block barrier; else a block per graph of P / 2 threads, at least 256 and at
+ * most 1024.  Integer arithmetic only, no atomics, no workspace.
+ * Limits, answered before any device call: G < 0, n < 1, d < 1, d >= n, n * d odd, max_attempts < 1, first_graph < 0 or a
+ * NULL output (G > 0) are KPGNN_EINVAL; d > KPGNN_RRG_MAX_DEGREE, n > KPGNN_RRG_MAX_NODES or n * d > KPGNN_RRG_MAX_STUBS
+ * are KPGNN_ELIMIT (d >= 5 accepts fewer than 3 pairings in 1000: DESIGN.md 5.31).  G == 0 returns KPGNN_OK without a launch.
+ * ---------------------------------------------------------------------------------------------- */
+enum { KPGNN_RRG_OK = 0, KPGNN_RRG_EXHAUSTED = 1 };
+#define KPGNN_RRG_MAX_DEGREE 4
+#define KPGNN_RRG_MAX_NODES 2048     /* (the bound of kpgnn_khop_large_*) */
+#define KPGNN_RRG_MAX_STUBS 8192     /* n * d: the 13 index bits of a key */
+#define KPGNN_RRG_WAVE_STUBS 256     /* n * d up to which a wavefront owns a graph */
+
+typedef struct kpgnn_rrg_desc {
+    int32_t G, n, d, max_attempts;  /* graphs of the call; nodes and degree of each; pairings tried per graph */
+    int64_t seed, first_graph;      /* the Philox key; the id of the call's graph 0 */
+    int64_t* edge_index;            /* device [2, G * n * d] contiguous */
+    int32_t* attempts;              /* device [G] */
+    int32_t* status;                /* device [G] */
+} kpgnn_rrg_desc;
+
+int kpgnn_random_regular_graphs(const kpgnn_rrg_desc* d, kpgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

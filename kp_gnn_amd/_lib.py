@@ -462,6 +462,17 @@ class CountLabelsDesc(ctypes.Structure):
     _fields_ = RdDesc._fields_ + [("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t)]     # (`out` is double [G,5] here)
 
 
+RRG_OK, RRG_EXHAUSTED = 0, 1                                            # include/kpgnn.h KPGNN_RRG_*
+RRG_MAX_DEGREE, RRG_MAX_NODES, RRG_MAX_STUBS, RRG_WAVE_STUBS = 4, 2048, 8192, 256    # KPGNN_RRG_MAX_DEGREE, _MAX_NODES, _MAX_STUBS, _WAVE_STUBS
+
+
+class RrgDesc(ctypes.Structure):
+    _fields_ = [
+        ("G", c_i32), ("n", c_i32), ("d", c_i32), ("max_attempts", c_i32), ("seed", c_i64), ("first_graph", c_i64),
+        ("edge_index", c_vp), ("attempts", c_vp), ("status", c_vp),
+    ]
+
+
 class AttnPoolDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i64), ("G", c_i32), ("D", c_i32),
@@ -590,6 +601,7 @@ SIGNATURES = {
     "kpgnn_graph_labels_large": (ctypes.c_int, [ctypes.POINTER(GraphLabelsDesc), c_vp]),
     "kpgnn_count_labels_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "kpgnn_count_labels": (ctypes.c_int, [ctypes.POINTER(CountLabelsDesc), c_vp]),
+    "kpgnn_random_regular_graphs": (ctypes.c_int, [ctypes.POINTER(RrgDesc), c_vp]),
     "kpgnn_vn_add_pool": (ctypes.c_int, [ctypes.POINTER(VnDesc), c_vp]),
     "kpgnn_dropout_fwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
     "kpgnn_dropout_bwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),

@@ -15,25 +15,13 @@
 // the block that FINISHES last (ticket, as in adam.hip) bumps state[1] - after every other block has read it.  A replayed
 // graph therefore draws a fresh mask on every replay.
 #include "kpgnn_common.h"
+#include "philox.h"
 
 namespace kpgnn {
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kMaxGrid = 2048;      // 256 CUs x 8 blocks: grid-stride beyond (and at most that many ticket arrivals)
-
-struct Philox4 { uint32_t w[4]; };
-
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return Philox4{{c0, c1, c2, c3}};
-}
 
 enum { OP_FWD = 0, OP_BWD = 1, OP_MASK = 2 };
 

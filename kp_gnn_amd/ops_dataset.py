@@ -1,14 +1,15 @@
 """The dataset ops over raw graphs (node_ptr, edge_ptr, edge_index): resistance_distance, graph_property_labels, count_labels,
-khop_transform; ops.py re-exports them.  One host program: RawGraphs validates, upload() moves the index arrays, a host-only
+khop_transform, and random_regular_graphs, which makes such graphs; ops.py re-exports them.  One host program: RawGraphs validates, upload() moves the index arrays, a host-only
 *_plan function of the graph sizes lists (entry point, ids, max_nodes, workspace_bytes) in launch order, run_plan() issues it,
 reads the status once, raises the op's refusals and returns the graphs left to the host route.  The descriptor, the status
 preset, the refusal texts and the fill stay with each op."""
+import collections
 import ctypes
 
 import numpy as np
 import torch
 
-from . import _lib, graph_count as GCN, graph_property as GP, khop_transform as KT
+from . import _lib, graph_count as GCN, graph_property as GP, khop_transform as KT, regular_graphs as RG
 from .raw_graphs import RawGraphs
 
 
@@ -414,3 +415,68 @@ def khop_transform(node_ptr, edge_ptr, edge_index, edge_attr, K, max_edge_attr_n
             if out[k] is not None:
                 out[k][n_dst] = host[k].to(dev)
     return out, torch.from_numpy(status)
+
+
+# ------------------------------------------------------------------------------------------------ random regular graphs
+RegularGraphs = collections.namedtuple("RegularGraphs", "node_ptr edge_ptr edge_index attempts exhausted route")
+RegularGraphs.__doc__ = """What random_regular_graphs returns: node_ptr / edge_ptr [G+1] host int64 arrays, edge_index [2, G n d]
+int64 on the call's device (LOCAL ids, (src, dst)-sorted per graph) - the triple ops.khop_transform and RawGraphs accept -
+attempts [G] host int32 (pairings drawn per graph; None on the networkx route), exhausted: the graphs (host int64 array) that
+used up max_attempts and were filled from networkx, and the route that served the call."""
+
+
+def regular_graphs_route(n, d, dev, route="auto"):
+    """The route random_regular_graphs takes: "auto" is the pairing model inside its limits - on the device where there is one,
+    else on the host, the same bits - and networkx beyond them (d >= 5, n > 2048, n * d > 8192)."""
+    if route not in ("auto", "device", "host", "networkx"):
+        raise ValueError(f"unknown route {route!r}")
+    if route != "auto":
+        return route
+    return "networkx" if not RG.within_limits(n, d) else "device" if dev.type == "cuda" else "host"
+
+
+def random_regular_graphs(G, n, d, seed, device, first_graph=0, route="auto", max_attempts=4096):
+    """G uniform random simple d-regular graphs on n nodes as raw graphs, a RegularGraphs record.  Graph g is a function of
+    (seed, first_graph + g, n, d) alone: the pairing model with rejection of include/kpgnn.h (kpgnn_random_regular_graphs).
+    route "device": one kpgnn_random_regular_graphs launch (csrc/regular_graphs.hip), then ONE read of attempts and status;
+    edge_index never leaves the device.  Beyond the kernel's limits it raises KpgnnError.  route "host":
+    regular_graphs.random_regular_graphs_host, the same bits from numpy, moved to `device` (which may be the CPU).  On both, a
+    graph that used up max_attempts pairings is filled from nx.random_regular_graph(d, n, seed + first_graph + g) inside the
+    same call and named in `exhausted` (at the default cap this has a probability below e^-55 for every served shape).
+    route "networkx": batch.regular_graphs(G, seed + first_graph, n, d) - another draw, networkx's Steger-Wormald procedure
+    on Python's Mersenne Twister, uniform only asymptotically.  "auto": regular_graphs_route.  An odd n * d or d >= n raises
+    ValueError on every route."""
+    G, n, d, seed, first_graph, max_attempts = int(G), int(n), int(d), int(seed), int(first_graph), int(max_attempts)
+    dev = torch.device(device)
+    route = regular_graphs_route(n, d, dev, route)
+    RG.check_arguments(G, n, d, max_attempts, first_graph)
+    m = n * d
+    if route == "networkx":
+        from .batch import regular_graphs
+        if G == 0:
+            node_ptr, edge_ptr, ei = np.zeros(1, np.int64), np.zeros(1, np.int64), np.zeros((2, 0), np.int64)
+        else:
+            node_ptr, edge_ptr, ei = regular_graphs(G, seed + first_graph, n=n, degree=d)
+        return RegularGraphs(node_ptr, edge_ptr, torch.from_numpy(ei).to(dev), None, np.zeros(0, np.int64), route)
+    if route == "host":
+        node_ptr, edge_ptr, ei, attempts, status = RG.random_regular_graphs_host(G, n, d, seed, first_graph, max_attempts)
+        ei = torch.from_numpy(ei).to(dev)
+    else:
+        if dev.type != "cuda":
+            raise _lib.KpgnnError("ops.random_regular_graphs(route='device') needs a GPU device: route='host' gives the same graphs")
+        ptr = np.arange(G + 1, dtype=np.int64)
+        node_ptr, edge_ptr = ptr * n, ptr * m
+        ei = torch.empty((2, G * m), dtype=torch.int64, device=dev)
+        back = torch.empty((2, G), dtype=torch.int32, device=dev)
+        desc = _lib.RrgDesc()
+        desc.G, desc.n, desc.d, desc.max_attempts, desc.seed, desc.first_graph = G, n, d, max_attempts, seed, first_graph
+        desc.edge_index, desc.attempts, desc.status = ei.data_ptr(), back[0].data_ptr(), back[1].data_ptr()
+        _lib.launch("kpgnn_random_regular_graphs", dev, ctypes.byref(desc))
+        attempts, status = back.cpu().numpy()                       # the one read
+    todo = np.flatnonzero(status != _lib.RRG_OK)
+    if todo.size:
+        from .batch import regular_graphs
+        cols = torch.from_numpy(np.concatenate([np.arange(g * m, (g + 1) * m) for g in todo])).to(dev)
+        fill = np.concatenate([regular_graphs(1, seed + first_graph + int(g), n=n, degree=d)[2] for g in todo], axis=1)
+        ei[:, cols] = torch.from_numpy(fill).to(dev)
+    return RegularGraphs(node_ptr, edge_ptr, ei, attempts, todo.astype(np.int64), route)

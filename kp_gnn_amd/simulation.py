@@ -1,6 +1,6 @@
 """The regular-graph simulation of the reference (run_simulation.py:96-178) on this project's parts: random R-regular graphs
-(batch.regular_graphs), the K-hop pre-transform on the device (ops.khop_transform), one mask-only K-hop GIN layer in eval mode
-(layers.KGINConv) and the collision rate of its node or graph embeddings (ops.collision_count).  The embeddings stay on the
+(batch.regular_graphs from networkx, or ops.random_regular_graphs on the device), the K-hop pre-transform on the device
+(ops.khop_transform), one mask-only K-hop GIN layer in eval mode (layers.KGINConv) and the collision rate of its node or graph embeddings (ops.collision_count).  The embeddings stay on the
 device from the forward to the count; what comes back to the host is two integers per (n, k)."""
 import time
 
@@ -59,7 +59,7 @@ class _Stage:
 
 
 def simulate(n_list, R=3, N=100, K=6, graph=False, hidden_size=16, seed=0, device=None, chunk_graphs=None,
-             return_outputs=False, timings=None):
+             return_outputs=False, timings=None, generator="networkx"):
     """run_simulation.py:96-116: {(n, k): collision rate} for every n of n_list and k = 1 .. K.  Per n the N random R-regular
     graphs are generated once (seeds seed .. seed + N - 1, x = ones); per k they are pre-transformed with
     (k, 10, 1, 1, 1, 1, "spd") on the device (graphs of up to 2048 nodes by the kernels, larger ones by the host route of the
@@ -67,7 +67,12 @@ def simulate(n_list, R=3, N=100, K=6, graph=False, hidden_size=16, seed=0, devic
     gradients over chunks of `chunk_graphs` graphs (default: as many as keep a chunk's K-hop edges within 2^24), the outputs are
     concatenated on the device - node rows, or one pooled row per graph with graph=True - and counted there.
     return_outputs: (rates, {(n, k): the [rows, hidden_size] device tensor}).  timings: a dict that receives the seconds per
-    stage (generate / pre_transform / forward / count), each fenced by device synchronises; None times nothing."""
+    stage (generate / pre_transform / forward / count), each fenced by device synchronises; None times nothing.
+    generator: "networkx", the default, is the reference's generator on the host (batch.regular_graphs); "device" draws the
+    graphs of each n with ops.random_regular_graphs(N, n, R, seed, route="device") - uniform random regular graphs from the
+    pairing model, another draw than networkx's - and every chunk is a slice of its device edge list: no graph visits the host."""
+    if generator not in ("networkx", "device"):
+        raise ValueError(f"unknown generator {generator!r}: 'networkx' or 'device'")
     from .layers import KGINConv
     dev = torch.device("cuda" if device is None else device)
     if dev.type != "cuda":
@@ -78,7 +83,10 @@ def simulate(n_list, R=3, N=100, K=6, graph=False, hidden_size=16, seed=0, devic
     for n in n_list:
         n = int(n)
         with _Stage(timings, "generate", dev):
-            node_ptr, edge_ptr, ei = regular_graphs(N, seed, n=n, degree=R)
+            if generator == "device":
+                node_ptr, edge_ptr, ei = ops.random_regular_graphs(N, n, R, seed, dev, first_graph=0, route="device")[:3]
+            else:
+                node_ptr, edge_ptr, ei = regular_graphs(N, seed, n=n, degree=R)
         for k in range(1, K + 1):
             torch.manual_seed(seed)
             model = KGINConv(hidden_size, k, pool=graph).to(dev).eval()
