@@ -1843,6 +1843,104 @@ typedef struct kpgnn_rrg_desc {
 
 int kpgnn_random_regular_graphs(const kpgnn_rrg_desc* d, kpgnn_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * The random graphs of the graph- and node-property dataset (csrc/property_graphs.hip; the same bits from
+ * kp_gnn_amd/property_graphs.py on the host): the reference's datasets/graph_generation.py generate_graph - ten graph types,
+ * a uniform relabelling, `randomize`, and a retry while a node has no neighbour - as a function of Philox words.  Graph g of
+ * a call is a function of (seed, first_graph + g, n_g, graph_type, flags) alone; no launch geometry enters.  The laws are the
+ * reference's; the stream is not (numpy's and Python's Mersenne Twister there), so the graphs are another draw.
+ *   words     W(stream, a, i) = the output (w0, w1, w2, w3) of Philox4x32-10 (as for kpgnn_random_regular_graphs) under the
+ *             key (seed & 0xFFFFFFFF, seed >> 32) at the counter (i, a << 4 | stream, id & 0xFFFFFFFF, id >> 32),
+ *             id = (uint64_t)(first_graph + g), a the attempt.  "Word i" of a stream is w0 of W(stream, a, i); PAIR also
+ *             uses w1 and w2 and SHUFFLE w1.  Streams: TYPE 0 (always a = 0), PARAM 1, PAIR 2, BA 3, TREE 4, ATTACH 5,
+ *             SHUFFLE 6, FEATURE 7, SOURCE 8.
+ *   below     below(w, L) = ((uint64_t)w * L) >> 32: uniform in [0, L) with a bias below L / 2^32 (L <= 8192 here).
+ *   No floating point enters a decision: every comparison is one of integers of at most 64 bits.
+ * Attempt a = 0, 1, .. of a graph of n nodes:
+ *   1 type      graph_type, or for KPGNN_PG_RANDOM (once per graph, kept over the attempts) x = below(TYPE word 0, 20) against
+ *               the reference's MIXTURE in twentieths: x < 4 ERDOS_RENYI, < 8 BARABASI_ALBERT, < 9 GRID, < 10 CAVEMAN,
+ *               < 13 TREE, < 14 LADDER, < 15 LINE, < 16 STAR, < 18 CATERPILLAR, else LOBSTER.
+ *   2 structure on canonical labels 0 .. n-1 (the position of a node in list(G) of the networkx constructor the reference calls).
+ *     ERDOS_RENYI      p = PARAM word 0; pair (i, j), i > j, numbered q = i (i - 1) / 2 + j, is an edge iff w2 of
+ *                      W(PAIR, a, q) < p (p as a 32-bit fraction is uniform, as the reference's degree / N).
+ *     BARABASI_ALBERT  m = 1 + below(PARAM word 0, n - 1).  A star with centre 0 and leaves 1 .. m; the list `repeated` =
+ *                      m times 0, then 1 .. m.  Node s = m + 1 .. n - 1 draws x = repeated[below(BA word t, len(repeated))],
+ *                      t = 0, 1, .. counting on across the whole graph, until it holds m DISTINCT targets x, joins them, and
+ *                      appends its targets in ASCENDING order and then m copies of s (networkx 3.x's procedure).
+ *     GRID             r = the largest divisor of n with r * r <= n, c = n / r: node i * c + j joins its right (j + 1 < c)
+ *                      and its lower (i + 1 < r) neighbour.
+ *     CAVEMAN          the same r: r cliques of n / r consecutive nodes (a prime n: the complete graph).
+ *     LADDER           h = n / 2: the paths 0 .. h-1 and h .. 2h-1, the rungs (i, i + h); an odd n adds node n - 1 joined to 0.
+ *     LINE             the path 0 - 1 - .. - n-1.            STAR  node 0 joined to every other.
+ *     TREE             degree(v) of a word v = the smallest k >= 1 with v * (2k+1)^2 < 2^32 * ((2k+1)^2 - 4), at most n
+ *                      (round(paretovariate(2)): P(1) = 5/9, P(k) = 4 / (2k-1)^2 - 4 / (2k+1)^2).  deg[i] = degree(TREE word
+ *                      i), i < n.  For s = 0, 1, ..: stop when sum(deg) == 2n - 2; the attempt is REJECTED when
+ *                      s == KPGNN_PG_TREE_SWAPS; else deg[below(TREE word n + 2s, n)] = degree(TREE word n + 2s + 1).  The
+ *                      graph is nx.degree_sequence_tree(deg): with I the number of degrees above 1, a path 0 .. I+1; its
+ *                      inner nodes 1 .. I take those degrees in ascending order and node b of degree k gets the next k - 2
+ *                      unused labels, from I + 2 on, as leaves.
+ *     CATERPILLAR      B = 1 + below(PARAM word 0, n - 1): the path 0 .. B-1; node i >= B joins below(ATTACH word i, B).
+ *     LOBSTER          B as above, F = B + 1 + below(PARAM word 1, n - B); node i in [B, F) joins below(ATTACH word i, B),
+ *                      node i in [F, n) joins B + below(ATTACH word i, F - B).
+ *   3 relabel   node i becomes the rank of its key ((w1 << 32 | w0) & ~127) | i of W(SHUFFLE, a, i) among the n keys: a
+ *               uniform permutation (no ties: the index is in the low 7 bits).  Skipped under KPGNN_PG_NO_SHUFFLE.
+ *   4 randomize the reference's `randomize`, with its sum of two uniforms: with e the edges so far, r = n (n - 1) / 2 - e and,
+ *               for the pair u > v of the NEW labels, t = w0 + w1 of W(PAIR, a, u (u - 1) / 2 + v) (33 bits),
+ *                 e <= r: an edge stays iff 10 t < 9 * 2^33;              a missing one appears iff 10 t r < e * 2^33;
+ *                 e >  r: an edge stays iff 10 t e < (10 e - r) * 2^33;   a missing one appears iff 10 t < 2^33.
+ *               Skipped under KPGNN_PG_NO_RANDOMIZE.
+ *   5 accept    iff every node has a neighbour; otherwise (or after a rejected TREE) a increases by one, and after
+ *               max_attempts attempts the graph is EXHAUSTED.
+ *   6 output    of the accepted attempt a: source = below(SOURCE word 0, n); feature[i] = (FEATURE word i >> 8) * 2^-24 as
+ *               float (exact); row u of the adjacency as two 64-bit words, bit v & 63 of word v >> 6.
+ * kpgnn_property_graphs_generate serves the n_ids graphs `graph_ids` of a call of G graphs and writes, for graph g with
+ * node_ptr[g] = its first row: rows [N, 2], features [N] and the columns g of info [5, G]: the DIRECTED edge count 2 e, the
+ * source, the type, the attempts made and the status.  An EXHAUSTED graph (and, so that a wrong plan cannot write out of
+ * bounds, a graph of fewer than 2 nodes or more than the launch's class holds, with attempts 0) gets the edge count 0, the
+ * source 0 and no rows or features.  max_nodes <= KPGNN_PG_WAVE_NODES and force_block == 0: a wavefront per graph, four
+ * graphs per 256-thread block, no block barrier; else a 256-thread block per graph (up to 128 nodes).  The class changes no bit.
+ * kpgnn_property_graphs_fill expands the rows of the same graphs into edge_index [2, E] int64, LOCAL ids, (src, dst)-sorted,
+ * graph g at the columns [edge_ptr[g], edge_ptr[g + 1]) of the caller's cumulative sum of info[0]; a graph whose status is
+ * not OK or whose count does not fill its columns exactly is skipped.  A wavefront per row, popcount prefixes, no atomics.
+ * Limits, answered before any device call: a NULL descriptor, G < 0, n_ids < 0 or > G, max_attempts < 1 or > 2^27,
+ * first_graph < 0, an unknown graph_type, unknown flag bits, max_nodes outside [1, 128] or a NULL array with G > 0 are
+ * KPGNN_EINVAL; any nodes[g] outside [KPGNN_PG_MIN_NODES, KPGNN_PG_MAX_NODES] is KPGNN_ELIMIT; G == 0 or n_ids == 0 returns
+ * KPGNN_OK without a launch.  No atomics, no workspace, and no floating point but the feature conversion.
+ * ---------------------------------------------------------------------------------------------- */
+enum { KPGNN_PG_OK = 0, KPGNN_PG_EXHAUSTED = 1 };
+#define KPGNN_PG_MIN_NODES 2
+#define KPGNN_PG_MAX_NODES 128       /* (the bound of kpgnn_graph_labels_large; the reference's splits go to 99) */
+#define KPGNN_PG_WAVE_NODES 64       /* nodes up to which a wavefront owns a graph */
+#define KPGNN_PG_TREE_SWAPS 5000     /* (the reference's tries=10000 is 5,000 swaps and then an exception) */
+enum { KPGNN_PG_RANDOM = 0, KPGNN_PG_ERDOS_RENYI = 1, KPGNN_PG_BARABASI_ALBERT = 2, KPGNN_PG_GRID = 3, KPGNN_PG_CAVEMAN = 5,
+       KPGNN_PG_TREE = 6, KPGNN_PG_LADDER = 7, KPGNN_PG_LINE = 8, KPGNN_PG_STAR = 9, KPGNN_PG_CATERPILLAR = 10,
+       KPGNN_PG_LOBSTER = 11 };                                          /* the reference's GraphType values */
+enum { KPGNN_PG_STREAM_TYPE = 0, KPGNN_PG_STREAM_PARAM = 1, KPGNN_PG_STREAM_PAIR = 2, KPGNN_PG_STREAM_BA = 3,
+       KPGNN_PG_STREAM_TREE = 4, KPGNN_PG_STREAM_ATTACH = 5, KPGNN_PG_STREAM_SHUFFLE = 6, KPGNN_PG_STREAM_FEATURE = 7,
+       KPGNN_PG_STREAM_SOURCE = 8 };
+#define KPGNN_PG_NO_SHUFFLE 1        /* flags: keep the canonical labels */
+#define KPGNN_PG_NO_RANDOMIZE 2      /* flags: keep the structure's edges */
+
+typedef struct kpgnn_pg_desc {
+    int32_t G, n_ids;               /* graphs of the call; graphs of this launch */
+    const int32_t* nodes;           /* HOST [G]: the node counts, checked before any device call */
+    const int64_t* node_ptr;        /* device [G+1]: their cumulative sum */
+    const int32_t* graph_ids;       /* device [n_ids], or NULL for the graphs 0 .. n_ids-1 */
+    int32_t max_nodes;              /* the launch's size class holds graphs up to this many nodes */
+    int32_t graph_type, flags, max_attempts;
+    int32_t force_block, reserved;  /* nonzero: the block class whatever max_nodes (the same bits; for tests) */
+    int64_t seed, first_graph;      /* the Philox key; the id of the call's graph 0 */
+    uint64_t* rows;                 /* device [N, 2] */
+    float* features;                /* device [N]           (_generate) */
+    int32_t* info;                  /* device [5, G]: edges | source | type | attempts | status */
+    const int64_t* edge_ptr;        /* device [G+1]         (_fill) */
+    int64_t* edge_index;            /* device [2, E]        (_fill) */
+    int64_t E;
+} kpgnn_pg_desc;
+
+int kpgnn_property_graphs_generate(const kpgnn_pg_desc* d, kpgnn_stream_t stream);
+int kpgnn_property_graphs_fill(const kpgnn_pg_desc* d, kpgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

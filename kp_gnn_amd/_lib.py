@@ -473,6 +473,23 @@ class RrgDesc(ctypes.Structure):
     ]
 
 
+PG_OK, PG_EXHAUSTED = 0, 1                                              # include/kpgnn.h KPGNN_PG_*
+PG_MIN_NODES, PG_MAX_NODES, PG_WAVE_NODES, PG_TREE_SWAPS = 2, 128, 64, 5000    # KPGNN_PG_MIN_NODES, _MAX_NODES, _WAVE_NODES, _TREE_SWAPS
+PG_TYPES = {"RANDOM": 0, "ERDOS_RENYI": 1, "BARABASI_ALBERT": 2, "GRID": 3, "CAVEMAN": 5, "TREE": 6, "LADDER": 7, "LINE": 8,
+            "STAR": 9, "CATERPILLAR": 10, "LOBSTER": 11}                # the reference's GraphType values
+PG_STREAMS = {"TYPE": 0, "PARAM": 1, "PAIR": 2, "BA": 3, "TREE": 4, "ATTACH": 5, "SHUFFLE": 6, "FEATURE": 7, "SOURCE": 8}
+PG_NO_SHUFFLE, PG_NO_RANDOMIZE = 1, 2                                   # KPGNN_PG_NO_SHUFFLE, _NO_RANDOMIZE (flags)
+
+
+class PgDesc(ctypes.Structure):
+    _fields_ = [
+        ("G", c_i32), ("n_ids", c_i32), ("nodes", c_vp), ("node_ptr", c_vp), ("graph_ids", c_vp),
+        ("max_nodes", c_i32), ("graph_type", c_i32), ("flags", c_i32), ("max_attempts", c_i32),
+        ("force_block", c_i32), ("reserved", c_i32), ("seed", c_i64), ("first_graph", c_i64),
+        ("rows", c_vp), ("features", c_vp), ("info", c_vp), ("edge_ptr", c_vp), ("edge_index", c_vp), ("E", c_i64),
+    ]
+
+
 class AttnPoolDesc(ctypes.Structure):
     _fields_ = [
         ("N", c_i64), ("G", c_i32), ("D", c_i32),
@@ -602,6 +619,8 @@ SIGNATURES = {
     "kpgnn_count_labels_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "kpgnn_count_labels": (ctypes.c_int, [ctypes.POINTER(CountLabelsDesc), c_vp]),
     "kpgnn_random_regular_graphs": (ctypes.c_int, [ctypes.POINTER(RrgDesc), c_vp]),
+    "kpgnn_property_graphs_generate": (ctypes.c_int, [ctypes.POINTER(PgDesc), c_vp]),
+    "kpgnn_property_graphs_fill": (ctypes.c_int, [ctypes.POINTER(PgDesc), c_vp]),
     "kpgnn_vn_add_pool": (ctypes.c_int, [ctypes.POINTER(VnDesc), c_vp]),
     "kpgnn_dropout_fwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),
     "kpgnn_dropout_bwd": (ctypes.c_int, [ctypes.POINTER(DropoutDesc), c_vp]),

@@ -12,6 +12,7 @@ nodes keeps the reference's answer, overflow included (an overflowed product mak
 rule is "every ordered pair has a walk of length exactly 2^m", not connectivity: a connected bipartite graph answers False.
 An asymmetric (directed) list takes max(axis=0) over the directed distances and np.linalg.eig, as the reference does.
 """
+import collections
 import math
 
 import numpy as np
@@ -124,6 +125,44 @@ def normalize_labels(node_labels, graph_labels, node_ptr, train_ids):
     max_node = node_labels[rows.to(node_labels.device)].max(0)[0]
     max_graph = graph_labels[ids.to(graph_labels.device)].max(0)[0]
     return node_labels / max_node, graph_labels / max_graph
+
+
+GraphPropertySplit = collections.namedtuple("GraphPropertySplit", "node_ptr edge_ptr edge_index x pos y")
+
+
+def generate_split(nodes, seed, device, graph_type="RANDOM", first_graph=0, route="auto", large="device"):
+    """One split of the dataset from its seed (the reference's GenerateGraphPropertyDataset for one list of node counts): the
+    graphs of ops.property_graphs(nodes, seed, device, graph_type, first_graph, route), their labels by
+    ops.graph_property_labels on the same tensors (route and `large` passed on) and their inputs, as (node_ptr, edge_ptr: host
+    int64; edge_index [2,E] int64, x [N,2] float32 = source_features, pos [N,3] float32 node labels, y [G,3] float32 graph
+    labels: on `device`) - what normalize_labels and KHopDataset.from_graphs(pos=) take.  KpgnnError if a graph used up its
+    attempts.  On a GPU device no graph exists on the host at any point."""
+    from . import _lib, ops_dataset
+    g = ops_dataset.property_graphs(nodes, seed, device, graph_type=graph_type, first_graph=first_graph, route=route)
+    if g.exhausted.size:
+        raise _lib.KpgnnError(f"graph {int(g.exhausted[0])} (and {g.exhausted.size - 1} more) found no graph without an isolated node")
+    pos, y = ops_dataset.graph_property_labels(g.node_ptr, g.edge_ptr, g.edge_index, g.features, g.source, device,
+                                               route=g.route, large=large)
+    return GraphPropertySplit(g.node_ptr, g.edge_ptr, g.edge_index, source_features(g.features, g.source, g.node_ptr), pos, y)
+
+
+def reference_splits(extrapolation=False):
+    """The node counts of the reference's splits (GraphPropertyDataset.py genereate_dataset), a dict of int64 arrays in the
+    reference's order - the sizes of a split in turn, all graphs of a size together.  "train": 512 graphs of each size
+    15 .. 24.  "val" and "test": 128 and 256 graphs of each size 15 .. 19 - the reference pairs its FIVE counts with the first
+    five sizes of range(15, 25).  With extrapolation, instead of "test", the nine splits "test-(20,25)", "test-(25,30)",
+    "test-(30,35)", "test-(35,40)", "test-(40,45)", "test-(45,50)", "test-(60,65)", "test-(75,80)" and "test-(95,100)" of
+    256 graphs of each of their five sizes."""
+    def counts(per, sizes):
+        return np.repeat(np.asarray(sizes, dtype=np.int64), per)
+
+    out = {"train": counts(512, range(15, 25)), "val": counts(128, range(15, 20))}
+    if not extrapolation:
+        out["test"] = counts(256, range(15, 20))
+        return out
+    for lo in (20, 25, 30, 35, 40, 45, 60, 75, 95):
+        out[f"test-({lo},{lo + 5})"] = counts(256, range(lo, lo + 5))
+    return out
 
 
 def source_features(x_feature, source, node_ptr):

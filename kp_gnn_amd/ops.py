@@ -8,8 +8,9 @@ import torch
 
 from . import _lib
 from ._lib import MODE_GCN, MODE_GIN, MODE_GINPLUS, MODE_SUM, LaunchTimer, set_launch_timer  # noqa: F401
-from .ops_dataset import (COUNT_LABELS_AUTO, GRAPH_LABELS_AUTO, RegularGraphs, count_labels, count_labels_launch,  # noqa: F401
-                          graph_labels_launch, graph_property_labels, khop_transform, random_regular_graphs, resistance_distance)
+from .ops_dataset import (COUNT_LABELS_AUTO, GRAPH_LABELS_AUTO, PROPERTY_GRAPHS_AUTO, PropertyGraphs, RegularGraphs,  # noqa: F401
+                          count_labels, count_labels_launch, graph_labels_launch, graph_property_labels, khop_transform,
+                          property_graphs, random_regular_graphs, resistance_distance)
 
 _SQRT1_2 = 0.7071067811865476
 _INV_SQRT_2PI = 0.3989422804014327

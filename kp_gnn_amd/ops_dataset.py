@@ -1,5 +1,5 @@
 """The dataset ops over raw graphs (node_ptr, edge_ptr, edge_index): resistance_distance, graph_property_labels, count_labels,
-khop_transform, and random_regular_graphs, which makes such graphs; ops.py re-exports them.  One host program: RawGraphs validates, upload() moves the index arrays, a host-only
+khop_transform, and random_regular_graphs and property_graphs, which make such graphs; ops.py re-exports them.  One host program: RawGraphs validates, upload() moves the index arrays, a host-only
 *_plan function of the graph sizes lists (entry point, ids, max_nodes, workspace_bytes) in launch order, run_plan() issues it,
 reads the status once, raises the op's refusals and returns the graphs left to the host route.  The descriptor, the status
 preset, the refusal texts and the fill stay with each op."""
@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, graph_count as GCN, graph_property as GP, khop_transform as KT, regular_graphs as RG
+from . import _lib, graph_count as GCN, graph_property as GP, khop_transform as KT, property_graphs as PG, regular_graphs as RG
 from .raw_graphs import RawGraphs
 
 
@@ -480,3 +480,87 @@ def random_regular_graphs(G, n, d, seed, device, first_graph=0, route="auto", ma
         fill = np.concatenate([regular_graphs(1, seed + first_graph + int(g), n=n, degree=d)[2] for g in todo], axis=1)
         ei[:, cols] = torch.from_numpy(fill).to(dev)
     return RegularGraphs(node_ptr, edge_ptr, ei, attempts, todo.astype(np.int64), route)
+
+
+# ------------------------------------------------------------------------------------------------ graph-property graphs
+PROPERTY_GRAPHS_AUTO = "device"   # property_graphs(route="auto") where there is a device: DESIGN.md 5.32 has the measurement behind it
+
+PropertyGraphs = collections.namedtuple("PropertyGraphs", "node_ptr edge_ptr edge_index features source types attempts exhausted route")
+PropertyGraphs.__doc__ = """What property_graphs returns: node_ptr / edge_ptr [G+1] host int64 arrays, edge_index [2, E] int64 (LOCAL
+ids, (src, dst)-sorted per graph) and features [N] float32 on the call's device - with source [G] (host int32) what
+ops.graph_property_labels takes, and the triple what ops.khop_transform and RawGraphs accept - types [G] and attempts [G]
+host int32, exhausted: the graphs (host int64 array) that used up max_attempts and have no edges, and the route that served
+the call."""
+
+
+def property_graphs_plan(nodes):
+    """The launches of property_graphs: the wavefront class (n <= PG_WAVE_NODES) and the block class, each sized for its
+    largest member."""
+    return size_classes("kpgnn_property_graphs", nodes, (_lib.PG_WAVE_NODES, _lib.PG_MAX_NODES), largest_member(_lib.PG_MAX_NODES))
+
+
+def property_graphs(nodes, seed, device, graph_type="RANDOM", first_graph=0, route="auto", max_attempts=4096, randomize=True, shuffle=True):
+    """The random graphs of the reference's graph- and node-property dataset (datasets/graph_generation.py generate_graph) as
+    raw graphs with their node features and source nodes, a PropertyGraphs record.  nodes: an int or a length-G sequence of
+    node counts in [2, 128] (ValueError beyond, whatever the route); graph_type: a name of _lib.PG_TYPES or its id.  Graph g
+    is a function of (seed, first_graph + g, nodes[g], graph_type, randomize, shuffle) alone: the definition of
+    include/kpgnn.h (kpgnn_property_graphs_generate), the reference's laws on a Philox stream - another draw than the
+    reference's.
+    route "device": the graphs are bucketed by size on the host, one kpgnn_property_graphs_generate launch per class (n <= 64:
+    a wavefront per graph; n <= 128: a block per graph), ONE read of the [5, G] block of edge counts, sources, types, attempts
+    and statuses, the cumulative sum on the host, and one kpgnn_property_graphs_fill launch per class; edge_index and features
+    never leave the device.  route "host": property_graphs.property_graphs_host, the same bits from numpy, moved to `device`
+    (which may be the CPU).  "auto": PROPERTY_GRAPHS_AUTO on a GPU device, else the host.  A graph that used up max_attempts
+    is named in `exhausted` and has no edges (STAR at 128 nodes, the slowest case, keeps all its leaves attached with
+    probability 0.98^127: once in 13 attempts; 4096 rejections in a row have a probability below e^-300)."""
+    if route not in ("auto", "device", "host"):
+        raise ValueError(f"unknown route {route!r}")
+    nodes = PG.check_nodes(nodes)
+    t = PG.type_id(graph_type)
+    seed, first_graph, max_attempts = int(seed), int(first_graph), int(max_attempts)
+    if max_attempts < 1 or max_attempts > 1 << 27 or first_graph < 0:
+        raise ValueError(f"bad max_attempts={max_attempts} first_graph={first_graph}")
+    dev = torch.device(device)
+    if route == "auto":
+        route = PROPERTY_GRAPHS_AUTO if dev.type == "cuda" else "host"
+    G = nodes.shape[0]
+    if route == "host":
+        node_ptr, edge_ptr, ei, feat, source, types, attempts, status = PG.property_graphs_host(
+            nodes, seed, t, first_graph, max_attempts, randomize, shuffle)
+        return PropertyGraphs(node_ptr, edge_ptr, torch.from_numpy(ei).to(dev), torch.from_numpy(feat).to(dev), source, types,
+                              attempts, np.flatnonzero(status != _lib.PG_OK).astype(np.int64), route)
+    if dev.type != "cuda":
+        raise _lib.KpgnnError("ops.property_graphs(route='device') needs a GPU device: route='host' gives the same graphs")
+    node_ptr = np.concatenate([[0], np.cumsum(nodes)]).astype(np.int64)
+    N = int(node_ptr[-1])
+    feat = torch.zeros(N, dtype=torch.float32, device=dev)
+    if G == 0:
+        z = np.zeros(0, dtype=np.int32)
+        return PropertyGraphs(node_ptr, np.zeros(1, np.int64), torch.zeros((2, 0), dtype=torch.int64, device=dev), feat, z, z, z,
+                              np.zeros(0, np.int64), route)
+    nodes32 = np.ascontiguousarray(nodes.astype(np.int32))
+    nptr = torch.from_numpy(node_ptr).to(dev)
+    rows = torch.empty((N, 2), dtype=torch.int64, device=dev)
+    info = torch.empty((5, G), dtype=torch.int32, device=dev)
+    d = _lib.PgDesc()
+    d.G, d.nodes, d.node_ptr = G, nodes32.ctypes.data, nptr.data_ptr()
+    d.graph_type, d.max_attempts, d.seed, d.first_graph = t, max_attempts, seed, first_graph
+    d.flags = (0 if shuffle else _lib.PG_NO_SHUFFLE) | (0 if randomize else _lib.PG_NO_RANDOMIZE)
+    d.rows, d.features, d.info = rows.data_ptr(), feat.data_ptr(), info.data_ptr()
+    plan = [(ids, cap, torch.from_numpy(ids.astype(np.int32)).to(dev)) for _, ids, cap, _ in property_graphs_plan(nodes)]
+
+    def run(entry):
+        for ids, cap, ids_d in plan:
+            d.graph_ids, d.n_ids, d.max_nodes = ids_d.data_ptr(), ids.size, cap
+            _lib.launch(entry, dev, ctypes.byref(d))
+
+    run("kpgnn_property_graphs_generate")
+    counts, source, types, attempts, status = info.cpu().numpy()        # the one read
+    edge_ptr = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64)
+    E = int(edge_ptr[-1])
+    ei = torch.empty((2, E), dtype=torch.int64, device=dev)
+    eptr = torch.from_numpy(edge_ptr).to(dev)
+    d.edge_ptr, d.edge_index, d.E = eptr.data_ptr(), ei.data_ptr() if E else None, E
+    run("kpgnn_property_graphs_fill")
+    return PropertyGraphs(node_ptr, edge_ptr, ei, feat, source.copy(), types.copy(), attempts.copy(),
+                          np.flatnonzero(status != _lib.PG_OK).astype(np.int64), route)
